@@ -7,9 +7,13 @@ tiles, bf16 compute (f32 accumulate, f32 master weights), batch 4 per GPU, pure 
 scaling). One step = prep -> forward -> BCE+Dice loss/grad -> backward -> RCCL gradient all-reduce
 (N>1, bucketed, overlapped with backward) -> Adam, on inputs already resident in HBM.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
        (N>1: python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N)
-Rank 0 prints ONE JSON line (plus `roofline` and `cpu_baseline` objects).
+Rank 0 prints ONE JSON line. A plain run sets up, warms up, times the K steps, writes its outputs if asked to and
+prints the line. --full adds the legs that take work of their own: the `roofline` object (per-launch event timing
+in the last warm-up step, around the dominant kernel in the timed steps and in POST_STEPS steps after them), the
+`cpu_baseline` object (the oracle on the host cores and the same workload on the GPU) and the `dice_val` object
+(a training run to Dice@val); --no-cpu-baseline / --no-dice leave one of them out of a --full run.
 """
 import argparse
 import json
@@ -35,8 +39,12 @@ def parse():
     p.add_argument("--levels", type=int, default=5)
     p.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
     p.add_argument("--cpad", type=lambda v: tuple(int(x) for x in v.split(",")), default=None, help="adipose_v3 channel-stride granule (default 64 for bf16)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-dice", action="store_true", help="skip the Dice@val leg (profiling runs)")
+    p.add_argument("--full", action="store_true",
+                   help="also measure the roofline (per-launch event timing), the CPU baseline and Dice@val")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last of them computed as DIR/<name>.npy (rank 0)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline leg")
+    p.add_argument("--no-dice", action="store_true", help="--full: skip the Dice@val leg (profiling runs)")
     p.add_argument("--dice-steps", type=int, default=2000,
                    help="Dice@val leg: training steps (a fixed count, so the value is one number per build on any box)")
     p.add_argument("--dice-seconds", type=float, default=90.0,
@@ -191,6 +199,38 @@ def committed_traffic(kernel, workload, build):
     return hits[0] if hits else (None, None, None)
 
 
+def roofline(summ, psumm, step_ms, wl, build):
+    """--full: the roofline object of the result line. summ: the LaunchTimer summary of the timed region (the dominant
+    kernel's launches), psumm: that of the POST_STEPS steps after it (every GEMM launch), step_ms: ms_per_step."""
+    # roofline of the dominant kernel: the GEMM kernel instantiation with the largest total time
+    # (names as rocprofv3 prints them; profiles/ holds the matching --kernel-trace --stats summary)
+    dom = max(summ.items(), key=lambda kv: kv[1][2])
+    (kname, dcode), (n, flops, ms, abytes) = dom
+    dname = {0: "f32", 1: "bf16", 2: "fp8"}[dcode]
+    achieved = flops / (ms * 1e-3) / 1e12
+    # (per step: POST_STEPS steps after the timed region, every GEMM launch timed)
+    per_kernel = {k[0]: {"launches": v[0], "avg_ms": round(v[2] / v[0], 4),
+                         "tflops": round(v[1] / (v[2] * 1e-3) / 1e12, 2),
+                         "alg_gbs": round(v[3] / (v[2] * 1e-3) / 1e9, 1),
+                         "share_of_step": round(v[2] / POST_STEPS / step_ms, 4)}
+                  for k, v in sorted(psumm.items(), key=lambda kv: -kv[1][2])}
+    traffic, tsrc, same_build = committed_traffic(kname, wl, build)
+    alg_bytes = abytes / n
+    return {"bound": "mfma", "kernel": kname, "achieved": round(achieved, 2),
+            "peak": MI355X_PEAK[dname], "unit": "TFLOP/s", "frac": round(achieved / MI355X_PEAK[dname], 4),
+            "traffic": traffic, "traffic_unit": "bytes/launch (HBM, PMC)", "traffic_source": tsrc,
+            "traffic_same_build": same_build,
+            "algorithmic_bytes": round(alg_bytes),
+            "traffic_over_algorithmic": round(traffic / alg_bytes, 3) if traffic and alg_bytes else None,
+            "avg_launch_ms": round(ms / n, 4), "launches": n,
+            "flops_per_launch": round(flops / n / 1e9, 3),
+            "timing": ("the dominant kernel's launches of the timed region (HIP event pairs on its stream); "
+                       f"per_kernel and the GEMM totals from {POST_STEPS} steps after it with every GEMM launch timed"),
+            "gemm_share_of_step": round(sum(v[2] for v in psumm.values()) / POST_STEPS / step_ms, 4),
+            "gemm_tflops_all": round(sum(v[1] for v in psumm.values()) / (sum(v[2] for v in psumm.values()) * 1e-3) / 1e12, 2),
+            "per_kernel": per_kernel}
+
+
 def dice_leg(args):
     """Dice@val of THIS build, measured in this process after the timed steps (round-4 VERDICT item 5): a fresh
     network of the benched workload (seed 865) trains --dice-steps steps (2000; round 6: a step count instead of 45 s,
@@ -211,6 +251,38 @@ def dice_leg(args):
     out["curve"] = [(c["step"], c["dice_val"]) for c in r["curve"]]
     out["same_build"] = True   # (measured by this process on the library it benched)
     return out
+
+
+DUMP_MAX_ELEMS = 1 << 21   # per dumped array (8 MB as float32): at most 5 arrays, so a dump stays under 64 MB
+METRIC_NAMES = ("loss", "main_out_loss", "main_out_dice_coef", "main_out_binary_accuracy")
+
+
+def dump_outputs(path, args, net, met):
+    """--dump-outputs: what the last timed step left for the caller of Trainer.train_step, as <path>/<name>.npy:
+    the heads' predictions of that step (main_out, and aux_out1 / aux_out2 of adipose_v3), the parameter gradients
+    (param_grads) and the parameters after the Adam update (params), both in the flat buffer's order, as float32;
+    and the metrics Trainer.read_metrics returns (metrics: float64, in the order of METRIC_NAMES). An array of
+    more than DUMP_MAX_ELEMS elements is written as a sample at fixed positions (seeded by the array's size, so the
+    same arguments always pick the same elements), in flat row-major order."""
+    import numpy as np
+    import torch
+
+    a = net.acts(args.batch)
+    if args.preset == "unet_bn":
+        arrays = {"main_out": a["p"]}
+    else:
+        arrays = {"main_out": a["p_main"]}
+        if net.ds:
+            arrays.update(aux_out1=a["p_aux1"], aux_out2=a["p_aux2"])
+    arrays.update(param_grads=net.ps.grad, params=net.ps.flat)
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        n = t.numel()
+        if n > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(n).integers(0, n, DUMP_MAX_ELEMS))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.detach().float().cpu().numpy())
+    np.save(os.path.join(path, "metrics.npy"), np.array([met[k] for k in METRIC_NAMES], np.float64))
 
 
 def main():
@@ -262,13 +334,13 @@ def main():
     x = torch.from_numpy((xs - mean) / (std + 1e-10)).to(dev).contiguous()
     y = torch.from_numpy(ys).to(dev).contiguous()
 
-    # the last warm-up step times every GEMM launch to find the dominant kernel; the timed region then brackets
-    # only that kernel's launches with event pairs (each pair costs the step ~4 us: all ~65 of a unet_bn step
-    # cost it 1.3 %, profiles/r06l_timer_probe.log), and the other kernels' figures come from POST_STEPS
-    # steps after the timed region with every launch timed
+    # --full: the last warm-up step times every GEMM launch to find the dominant kernel; the timed region then
+    # brackets only that kernel's launches with event pairs (each pair costs the step ~4 us: all ~65 of a unet_bn
+    # step cost it 1.3 %, profiles/r06l_timer_probe.log), and the other kernels' figures come from POST_STEPS
+    # steps after the timed region with every launch timed. A plain run times no launch.
     dom_name = None
     for i in range(args.warmup):
-        wt = ops.LaunchTimer() if i == args.warmup - 1 else None
+        wt = ops.LaunchTimer() if args.full and i == args.warmup - 1 else None
         if wt is not None:
             ops.set_launch_timer(wt)
         tr.train_step(x, y)
@@ -279,11 +351,12 @@ def main():
                 dom_name = max(ws.items(), key=lambda kv: kv[1][2])[0][0]
     torch.cuda.synchronize()
 
-    timer = ops.LaunchTimer(only=dom_name)
+    timer = ops.LaunchTimer(only=dom_name) if args.full else None
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
-    ops.set_launch_timer(timer)
+    if timer is not None:
+        ops.set_launch_timer(timer)
     t0 = time.perf_counter()
     for _ in range(args.steps):
         tr.train_step(x, y)
@@ -291,7 +364,8 @@ def main():
     if world > 1:
         dist.barrier()
     t1 = time.perf_counter()
-    ops.set_launch_timer(None)
+    if timer is not None:
+        ops.set_launch_timer(None)
     elapsed = t1 - t0
     comm = None
     if world > 1:   # max over ranks; the per-rank times and the communicator's own rank count go into the line
@@ -305,50 +379,44 @@ def main():
         elapsed = max(v.item() for v in per_rank)
         world = dist.get_world_size()
     met = tr.read_metrics()
+    if args.dump_outputs and rank == 0:   # (before any further step moves the parameters)
+        dump_outputs(args.dump_outputs, args, net, met)
 
-    summ = timer.summary()
-    post = ops.LaunchTimer()   # (every rank: the steps all-reduce)
-    ops.set_launch_timer(post)
-    for _ in range(POST_STEPS):
-        tr.train_step(x, y)
-    ops.set_launch_timer(None)
-    psumm = post.summary()
+    summ = psumm = None
+    if args.full:
+        summ = timer.summary()
+        post = ops.LaunchTimer()   # (every rank: the steps all-reduce)
+        ops.set_launch_timer(post)
+        for _ in range(POST_STEPS):
+            tr.train_step(x, y)
+        ops.set_launch_timer(None)
+        psumm = post.summary()
     if rank != 0:
         if world > 1:
             dist.destroy_process_group()
         return
     tiles = B * world * args.steps * (S / 1024.0) ** 2
     value = tiles / elapsed
-    # roofline of the dominant kernel: the GEMM kernel instantiation with the largest total time
-    # (names as rocprofv3 prints them; profiles/ holds the matching --kernel-trace --stats summary)
-    dom = max(summ.items(), key=lambda kv: kv[1][2])
-    (kname, dcode), (n, flops, ms, abytes) = dom
-    dname = {0: "f32", 1: "bf16", 2: "fp8"}[dcode]
-    achieved = flops / (ms * 1e-3) / 1e12
-    step_ms = elapsed * 1e3 / args.steps
-    # (per step: POST_STEPS steps after the timed region, every GEMM launch timed)
-    per_kernel = {k[0]: {"launches": v[0], "avg_ms": round(v[2] / v[0], 4),
-                         "tflops": round(v[1] / (v[2] * 1e-3) / 1e12, 2),
-                         "alg_gbs": round(v[3] / (v[2] * 1e-3) / 1e9, 1),
-                         "share_of_step": round(v[2] / POST_STEPS / step_ms, 4)}
-                  for k, v in sorted(psumm.items(), key=lambda kv: -kv[1][2])}
     wl = workload_label(args)
     build = _lib.lib().adp_source_hash().decode()[:16]
-    traffic, tsrc, same_build = committed_traffic(kname, wl, build)
-    alg_bytes = abytes / n
-    roof = {"bound": "mfma", "kernel": kname, "achieved": round(achieved, 2),
-            "peak": MI355X_PEAK[dname], "unit": "TFLOP/s", "frac": round(achieved / MI355X_PEAK[dname], 4),
-            "traffic": traffic, "traffic_unit": "bytes/launch (HBM, PMC)", "traffic_source": tsrc,
-            "traffic_same_build": same_build,
-            "algorithmic_bytes": round(alg_bytes),
-            "traffic_over_algorithmic": round(traffic / alg_bytes, 3) if traffic and alg_bytes else None,
-            "avg_launch_ms": round(ms / n, 4), "launches": n,
-            "flops_per_launch": round(flops / n / 1e9, 3),
-            "timing": ("the dominant kernel's launches of the timed region (HIP event pairs on its stream); "
-                       f"per_kernel and the GEMM totals from {POST_STEPS} steps after it with every GEMM launch timed"),
-            "gemm_share_of_step": round(sum(v[2] for v in psumm.values()) / POST_STEPS / step_ms, 4),
-            "gemm_tflops_all": round(sum(v[1] for v in psumm.values()) / (sum(v[2] for v in psumm.values()) * 1e-3) / 1e12, 2),
-            "per_kernel": per_kernel}
+    line = {
+        "metric": "1024^2 tiles/sec (train)", "value": round(value, 4), "unit": "tiles/s", "n_gpus": world,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.dtype,
+        "data": "synthetic (seeded histology-like tiles, resident in HBM)",
+        "config": {"workload": wl, "preset": args.preset, "levels": args.levels if args.preset == "unet_bn" else 4,
+                   "tile": S, "batch_per_gpu": B, "global_batch": B * world, "parallelism": f"dp{world}",
+                   "allreduce": args.allreduce if world > 1 else None},
+        "comm": comm,
+        "build": build,
+        "train_loss": round(met["loss"], 5),
+    }
+    if not args.full:
+        print(json.dumps(line), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
+    roof = roofline(summ, psumm, elapsed * 1e3 / args.steps, wl, build)
     cpu = None
     if world == 1 and not args.no_cpu_baseline:
         try:
@@ -373,19 +441,7 @@ def main():
             dice = dice_leg(args)
         except Exception as e:  # report, never fake
             dice = {"dice_val": None, "error": repr(e)}
-    line = {
-        "metric": "1024^2 tiles/sec (train)", "value": round(value, 4), "unit": "tiles/s", "n_gpus": world,
-        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3),
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.dtype,
-        "data": "synthetic (seeded histology-like tiles, resident in HBM)",
-        "config": {"workload": wl, "preset": args.preset, "levels": args.levels if args.preset == "unet_bn" else 4,
-                   "tile": S, "batch_per_gpu": B, "global_batch": B * world, "parallelism": f"dp{world}",
-                   "allreduce": args.allreduce if world > 1 else None},
-        "comm": comm,
-        "build": build,
-        "train_loss": round(met["loss"], 5), "dice_val": dice,
-        "roofline": roof, "cpu_baseline": cpu,
-    }
+    line.update(dice_val=dice, roofline=roof, cpu_baseline=cpu)
     print(json.dumps(line), flush=True)
     if world > 1:
         dist.destroy_process_group()

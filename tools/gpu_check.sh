@@ -2,6 +2,7 @@
 # One GPU-box pass (run from the repo root under gpurun): GPU parity tests, smoke(), the default bench
 # line, then the round profile (tools/profile_round.sh). Every GPU step has its own time limit and the
 # chain stops at the first failure. usage: bash tools/gpu_check.sh <profile-tag> [tests|bench|prof]...
+# The bench step runs bench.py --full (roofline, CPU baseline, Dice@val) and logs to $BENCH_LOG (default bench.log).
 set -uo pipefail
 TAG=${1:-r01}
 shift || true
@@ -13,7 +14,7 @@ for s in $STEPS; do
     tests) timeout -k 10 900 python -u -m pytest tests -m gpu --maxfail=25 -v --timeout 120 --timeout-method thread \
              > gpurun_out/gpu_tests.log 2>&1 ;;
     smoke) timeout -k 10 180 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/smoke.log 2>&1 ;;
-    bench) timeout -k 10 300 python bench.py > gpurun_out/bench.log 2>&1 ;;
+    bench) timeout -k 10 300 python bench.py --full > "${BENCH_LOG:-bench.log}" 2>&1 ;;
     prof) bash tools/profile_round.sh "$TAG" > gpurun_out/prof.log 2>&1 ;;
     converge) timeout -k 10 480 python bench_converge.py --fp8 > gpurun_out/converge.json 2> gpurun_out/converge.err ;;
     convergev3) timeout -k 10 480 python bench_converge.py --preset adipose_v3 --batch 2 \
