@@ -2,6 +2,7 @@
 #include <climits>
 #include <cstdarg>
 #include <cstdio>
+#include <cstring>
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <map>
@@ -14,6 +15,7 @@
 namespace adp {
 static thread_local std::string g_err;
 static thread_local char g_kernel[160] = "";
+static thread_local int g_ksplit_last = INT_MIN;   // (INT_MIN: no tap64 launch yet, read as unset)
 static thread_local hipStream_t g_launch_stream = nullptr;
 
 // Per-launch timing of the conv kernels (adp_timing_*): set_kernel, which every conv launcher calls right
@@ -44,6 +46,7 @@ static hipEvent_t pool_event() {
   return e;
 }
 void set_launch_stream(hipStream_t s) { g_launch_stream = s; }
+void set_ksplit_last(int ksplit) { g_ksplit_last = ksplit; }
 void set_kernel(const char* fmt, ...) {
   va_list ap;
   va_start(ap, fmt);
@@ -106,8 +109,14 @@ int resident_grid(const void* kernel, int threads, size_t smem) {
 }
 }  // namespace adp
 
+static const char kKsplitLast[] = "tap64_ksplit_last";
+
 extern "C" int adp_set_option(const char* name, int value) {
   if (!name) return -1;
+  if (!std::strcmp(name, kKsplitLast)) {
+    adp::set_error("adp_set_option: tap64_ksplit_last is a report (adp_get_option), not an option");
+    return -1;
+  }
   std::lock_guard<std::mutex> lk(adp::g_opt_mu);
   if (value == INT_MIN) adp::opts().erase(name);   // back to the built-in default
   else adp::opts()[name] = value;
@@ -115,9 +124,10 @@ extern "C" int adp_set_option(const char* name, int value) {
 }
 
 // the current value of an option (its default when unset: INT_MIN); also the library's report channel for test
-// hooks ("tap64_ksplit_last": the split-K factor of the last tap64 launch)
+// hooks ("tap64_ksplit_last": the split-K factor of the calling thread's last tap64 launch, kept outside the options)
 extern "C" int adp_get_option(const char* name) {
   if (!name) return INT_MIN;
+  if (!std::strcmp(name, kKsplitLast)) return adp::g_ksplit_last;
   std::lock_guard<std::mutex> lk(adp::g_opt_mu);
   auto it = adp::opts().find(name);
   return it == adp::opts().end() ? INT_MIN : it->second;

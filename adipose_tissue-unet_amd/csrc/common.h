@@ -123,38 +123,13 @@ int option(const char* name, int dflt);  // runtime switches set through adp_set
 int resident_grid(const void* kernel, int threads, size_t smem = 0);
 // name of the kernel the last conv launch of this thread used (adp_last_kernel), printf-style
 void set_kernel(const char* fmt, ...);
+// split-K factor of this thread's last tap64 forward launch, 0 = unsplit (read as adp_get_option("tap64_ksplit_last"))
+void set_ksplit_last(int ksplit);
 // per-launch timing (adp_timing): the stream of the conv launch in progress (set at the ABI entry), and the
 // end mark of its main kernel (call right after launching it; set_kernel marks the start)
 void set_launch_stream(hipStream_t s);
 void kernel_end();
-// Replicated per-channel accumulators for the BatchNorm sums (statistics of a conv output, or the
-// BN-backward dbeta/dgamma reductions). Atomics execute at the memory side and serialise per
-// address, so thousands of blocks adding into the same C values queue behind each other (measured:
-// ~17 ns per add per address, 1.75 ms per training step); blocks add into replica (block & 63)
-// instead and stat_fold() sums the replicas into the caller's accumulators and re-zeroes them.
-// The replicas are f64 (round 4): each producer adds f32 partials summed in a fixed order, and f64 sums
-// of them in the atomics' run-dependent order round to the same f32 (deterministic BatchNorm statistics).
-// Per device, lazily allocated and zeroed; launches that use it must be ordered on one stream.
-constexpr int STAT_REPL = 64, STAT_CMAX = 2048;
-double* stat_scratch();   // [STAT_REPL][2][STAT_CMAX] f64, or nullptr (error set) if allocation failed or a
-                         // deferred fold is pending
-// bn_defer_fold bookkeeping: a launch that leaves its sums in the replicas records (C, sum, stream); only the
-// adp_bn_finalize_fold with the same three may take the replicas next (stat_scratch_fold clears the record)
-int defer_fold_begin(int C, const float* sum, hipStream_t s);
-double* stat_scratch_fold(int C, const float* sum, hipStream_t s);
-int bn_fold_reset(hipStream_t s);   // adp_bn_fold_reset
-// dynamic tile claiming: a zeroed slot of CLAIM_INTS counters for one persistent launch (a ring of CLAIM_SLOTS per
-// device, handed out in turn; a launch leaves its slot zeroed again), or nullptr (error set)
-constexpr int CLAIM_SLOTS = 64, CLAIM_INTS = 512;
-int* claim_slot();
-// per-device growable scratch (slot 0: weight-gradient split partials / slabs, 1: dz of the unfused BN-backward
-// weight gradient, 2: metrics, 3: bias-gradient block sums); growing synchronises the device
-void* scratch(int slot, size_t bytes);
-// deferred weight-gradient slab reductions of a stream (adp_wgrad_defer / adp_wgrad_flush; conv_wgrad_tap64.hip)
-int wgrad_defer(hipStream_t s, int on);
-int wgrad_flush(hipStream_t s);
-int wgrad_release(hipStream_t s);
-int wgrad_arena_chunks(hipStream_t s);
+// sums the BatchNorm accumulator replicas (workspace.h stat_scratch) into dst0 / dst1 and re-zeroes them
 int stat_fold(int C, float* dst0, float* dst1, hipStream_t s);   // elementwise.hip
 // the same over replica channels [c0, c0 + C) into dst0[0..C) (and dst1 unless nullptr)
 int stat_fold_at(int c0, int C, float* dst0, float* dst1, hipStream_t s);

@@ -27,8 +27,6 @@
 
 #include "conv_common.h"
 
-extern "C" int adp_set_option(const char* name, int value);   // (abi.cpp)
-
 namespace {
 
 __device__ __attribute__((aligned(256))) uint4 tap64_zero_page[64];
@@ -660,7 +658,8 @@ void launch_cfg(FwdArgs& a, hipStream_t s) {
       const int sp = std::min(std::min(8, (256 * occ) / tiles), nk / 6);
       if (sp >= 2) {
         int* cnt = adp::claim_slot();
-        float* part = static_cast<float*>(adp::scratch(7, (size_t)tiles * sp * BM * BN * sizeof(float)));
+        float* part = static_cast<float*>(
+            adp::scratch(adp::Slot::KsplitPart, (size_t)tiles * sp * BM * BN * sizeof(float), s));
         if (cnt && part) {
           a.ksplit = sp;
           a.kcnt = cnt;
@@ -671,7 +670,7 @@ void launch_cfg(FwdArgs& a, hipStream_t s) {
       }
     }
   }
-  ::adp_set_option("tap64_ksplit_last", a.ksplit);   // (test hook, adp_get_option)
+  adp::set_ksplit_last(a.ksplit);   // (test hook, adp_get_option)
   const dim3 g(a.nblocks), b(WM * WN * 64);
   // buffer-resource loads need every operand below 2 GiB (32-bit offsets, T64_OOB reserved)
   const int es = a.f8 ? 1 : (a.f32 ? 4 : 2);

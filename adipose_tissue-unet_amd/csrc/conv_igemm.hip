@@ -1019,11 +1019,12 @@ void launch_bias_grad(const WgradArgs& a, hipStream_t s) {
   const int C = a.dy_mode == 0 ? a.Nout : a.Cps;
   const int G = C / 8, lanes = NT / G;
   const int blocks = (int)std::min<size_t>((Mp + lanes - 1) / lanes, 1024);
-  float* part = adp::option("wgrad_det", 1) && C % 4 == 0 ? adp::reduce_part(3, (size_t)blocks * C * sizeof(float), s)
-                                                           : nullptr;
+  const adp::Slabs part = adp::option("wgrad_det", 1) && C % 4 == 0
+                              ? adp::reduce_part(adp::Slot::BiasRows, (size_t)blocks * C * sizeof(float), s)
+                              : adp::Slabs{};
   hipLaunchKernelGGL(channel_sum_kernel<T>, dim3(blocks), dim3(NT), 0, s, Mp, C, a.dy_stride,
-                     reinterpret_cast<const T*>(a.dY), part ? part : a.dB, 0, part ? 1 : 0);
-  if (part) adp::slab_reduce(blocks, (size_t)C / 4, part, a.dB, s);
+                     reinterpret_cast<const T*>(a.dY), part.p ? part.p : a.dB, 0, part.p ? 1 : 0);
+  if (part.p) adp::slab_reduce(blocks, (size_t)C / 4, part, a.dB, s);
 }
 
 }  // namespace
@@ -1253,7 +1254,7 @@ int launch_wgrad(const adp_conv_desc* d, const adp_conv_io* io, const void* dY, 
     if (!(std::is_same<T, bf16>::value && adp::option("conv_fast", 2) == 2 && adp::wgrad_bna_fusable(a))) {
       a.bna_dA = nullptr;
       if (!dY) {   // dz not wanted by the caller: the two-launch form computes it in library scratch
-        dY = adp::scratch(1, (size_t)a.M * dy_stride * (std::is_same<T, bf16>::value ? 2 : 4));
+        dY = adp::scratch(adp::Slot::UnfusedDz, (size_t)a.M * dy_stride * (std::is_same<T, bf16>::value ? 2 : 4), s);
         if (!dY) return -2;
         a.dY = dY;
       }
@@ -1268,7 +1269,7 @@ int launch_wgrad(const adp_conv_desc* d, const adp_conv_io* io, const void* dY, 
       if (a.bna_dA) {   // no kernel took the fused form: dY = bn_bwd_apply(dA, z) first, then the fallback
         a.bna_dA = nullptr;
         if (!dY) {
-          dY = adp::scratch(1, (size_t)a.M * dy_stride * 2);
+          dY = adp::scratch(adp::Slot::UnfusedDz, (size_t)a.M * dy_stride * 2, s);
           if (!dY) return -2;
           a.dY = dY;
         }

@@ -817,7 +817,7 @@ void launch_f32cfg(WgradArgs& a, hipStream_t s) {
   const size_t slab = (size_t)a.Nout * a.Kpad;
   a.part = nullptr;
   if (splits > 1 && adp::option("wgrad_f32_partials", TN >= 256 ? 1 : 0))
-    a.part = static_cast<float*>(adp::scratch(0, slab * splits * sizeof(float)));
+    a.part = static_cast<float*>(adp::scratch(adp::Slot::WgradPart, slab * splits * sizeof(float), s));
   adp::set_kernel("igemm_wgrad_f32_kernel<%d, %d>", WN, WK);
   hipLaunchKernelGGL((igemm_wgrad_f32_kernel<WN, WK>), dim3(tiles * splits), dim3(WN * WK * 64), 0, s, a);
   adp::kernel_end();
@@ -845,14 +845,14 @@ int launch_wgrad_f32(WgradArgs& a, hipStream_t s) {
       a.Nout % 4 == 0 && a.dy_mode == 0 && a.K == 72 && a.Kpad >= 72 && a.Kpad % 4 == 0 && a.dy_stride % 4 == 0 &&
       a.dy_stride >= 64 && a.srcA && a.M > 0) {
     const int G = std::max(1, std::min(option("wgrad_f32_in1_grid", 256), (a.M + 31) / 32));
-    float* part = reduce_part(0, (size_t)G * a.Nout * a.Kpad * sizeof(float), s);
-    float* bpart = a.dB ? reduce_part(3, (size_t)G * a.Nout * sizeof(float), s) : nullptr;
-    if (part && (bpart || !a.dB)) {
+    const Slabs part = reduce_part(Slot::WgradPart, (size_t)G * a.Nout * a.Kpad * sizeof(float), s);
+    const Slabs bpart = a.dB ? reduce_part(Slot::BiasRows, (size_t)G * a.Nout * sizeof(float), s) : Slabs{};
+    if (part.p && (bpart.p || !a.dB)) {
       adp::set_kernel("wgrad_in1_f32_kernel");
-      hipLaunchKernelGGL(wgrad_in1_f32_kernel, dim3(G), dim3(512), 0, s, a, part, bpart);
+      hipLaunchKernelGGL(wgrad_in1_f32_kernel, dim3(G), dim3(512), 0, s, a, part.p, bpart.p);
       adp::kernel_end();
       slab_reduce(G, (size_t)a.Nout * a.Kpad / 4, part, a.dW, s);
-      if (bpart) {
+      if (bpart.p) {
         slab_reduce(G, (size_t)a.Nout / 4, bpart, a.dB, s);
         a.dB = nullptr;   // (done: the caller's channel-sum launch is skipped)
       }
@@ -934,7 +934,7 @@ int launch_wgrad_f32(WgradArgs& a, hipStream_t s) {
     // the bias gradient in the same pass (option wgrad_f32_bias): per-block rows [G0][Nout] (G0 = the blocks of
     // each chunk-0 combination), zeroed first (blocks without patches and idle waves write nothing), then the
     // fixed-order slab reduce into dB -- instead of a channel-sum launch that reads dY once more
-    a.bias_part = nullptr;
+    Slabs bias;   // (the handle of a.bias_part, for the reduce)
     int g0 = 0;
     if (a.dB && a.Nout % 4 == 0 && option("wgrad_f32_bias", 1)) {
       // (one row per block index of the chunk-0 combinations; a combination with fewer blocks leaves its other
@@ -944,17 +944,17 @@ int launch_wgrad_f32(WgradArgs& a, hipStream_t s) {
         g0 = 0;
         for (int c = 0; c < combos; c += nch) g0 = std::max(g0, a.zt_cstart[c + 1] - a.zt_cstart[c]);
       }
-      a.bias_part = reduce_part(3, (size_t)g0 * a.Nout * sizeof(float), s);
-      if (a.bias_part && hipMemsetAsync(a.bias_part, 0, (size_t)g0 * a.Nout * sizeof(float), s) != hipSuccess)
-        a.bias_part = nullptr;
+      bias = reduce_part(Slot::BiasRows, (size_t)g0 * a.Nout * sizeof(float), s);
+      if (bias.p && hipMemsetAsync(bias.p, 0, (size_t)g0 * a.Nout * sizeof(float), s) != hipSuccess) bias = Slabs{};
     }
+    a.bias_part = bias.p;
     t3 = t3 && a.zt_n;
     adp::set_kernel(t3 ? "igemm_wgrad_halo_f32_kernel<true>" : "igemm_wgrad_halo_f32_kernel<false>");
     if (t3) hipLaunchKernelGGL((igemm_wgrad_halo_f32_kernel<true>), dim3(grid), dim3(512), 0, s, a);
     else hipLaunchKernelGGL((igemm_wgrad_halo_f32_kernel<false>), dim3(grid), dim3(512), 0, s, a);
     if (a.bias_part) {
       adp::kernel_end();
-      slab_reduce(g0, (size_t)a.Nout / 4, a.bias_part, a.dB, s);
+      slab_reduce(g0, (size_t)a.Nout / 4, bias, a.dB, s);
       a.dB = nullptr;   // (done: the caller's channel-sum launch is skipped)
       a.bias_part = nullptr;
     }
@@ -976,12 +976,13 @@ int launch_wgrad_f32(WgradArgs& a, hipStream_t s) {
       const long long items = (long long)combos * a.Nimg * (a.Ho / HF_PH) * (a.Wo / HF_PW);
       const int grid = (int)std::max(1LL, std::min<long long>(items, option("wgrad_f32_dil_grid", 256)));
       a.zt_n = 0;
-      a.bias_part = nullptr;
+      Slabs bias;
       if (a.dB && a.Nout % 4 == 0 && option("wgrad_f32_bias", 1)) {
-        a.bias_part = reduce_part(3, (size_t)grid * a.Nout * sizeof(float), s);
-        if (a.bias_part && hipMemsetAsync(a.bias_part, 0, (size_t)grid * a.Nout * sizeof(float), s) != hipSuccess)
-          a.bias_part = nullptr;
+        bias = reduce_part(Slot::BiasRows, (size_t)grid * a.Nout * sizeof(float), s);
+        if (bias.p && hipMemsetAsync(bias.p, 0, (size_t)grid * a.Nout * sizeof(float), s) != hipSuccess)
+          bias = Slabs{};
       }
+      a.bias_part = bias.p;
       adp::set_kernel("igemm_wgrad_halo_f32_dil_kernel<%d>", split);
       if (split == 1) hipLaunchKernelGGL((igemm_wgrad_halo_f32_dil_kernel<1>), dim3(grid), dim3(512), 0, s, a);
       else if (split == 2) hipLaunchKernelGGL((igemm_wgrad_halo_f32_dil_kernel<2>), dim3(grid), dim3(512), 0, s, a);
@@ -989,7 +990,7 @@ int launch_wgrad_f32(WgradArgs& a, hipStream_t s) {
       else hipLaunchKernelGGL((igemm_wgrad_halo_f32_dil_kernel<8>), dim3(grid), dim3(512), 0, s, a);
       if (a.bias_part) {
         adp::kernel_end();
-        slab_reduce(grid, (size_t)a.Nout / 4, a.bias_part, a.dB, s);
+        slab_reduce(grid, (size_t)a.Nout / 4, bias, a.dB, s);
         a.dB = nullptr;
         a.bias_part = nullptr;
       }

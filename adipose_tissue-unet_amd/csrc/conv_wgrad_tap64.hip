@@ -17,10 +17,7 @@
 // pixel rows advance by 64 per stage with incremental (image, y, x) coordinates — no divisions in
 // the loop.
 #include "conv_common.h"
-#include <map>
-#include <mutex>
 #include <type_traits>
-#include <vector>
 
 namespace {
 
@@ -1799,68 +1796,6 @@ __global__ void wgrad_reduce_kernel(int splits, size_t slab, const float4* part,
   }
 }
 
-// Fixed-order sum of G partial slabs into dW (dW[i] += sum_g part[g][i]): a 256-thread block takes 32 float4
-// elements; its 8 thread groups sum consecutive slab ranges [g0, g1) in order, and group 0 adds the 8 range sums in
-// order. The association depends only on G, so two runs give the same bits (unlike f32 atomics).
-__device__ __forceinline__ void slab_reduce_block(int G, size_t n4, const float4* __restrict__ part,
-                                                  float4* __restrict__ dW, int blk, float4 (&ps)[8][32]) {
-  const int e = threadIdx.x & 31, j = threadIdx.x >> 5;
-  const size_t i = (size_t)blk * 32 + e;
-  const int per = (G + 7) / 8, g0 = min(G, j * per), g1 = min(G, g0 + per);
-  float4 acc = {0.f, 0.f, 0.f, 0.f};
-  if (i < n4) {
-    int g = g0;
-    for (; g + 4 <= g1; g += 4) {   // four loads in flight, added in order
-      const float4 v0 = part[(size_t)g * n4 + i], v1 = part[(size_t)(g + 1) * n4 + i];
-      const float4 v2 = part[(size_t)(g + 2) * n4 + i], v3 = part[(size_t)(g + 3) * n4 + i];
-      acc.x += v0.x; acc.y += v0.y; acc.z += v0.z; acc.w += v0.w;
-      acc.x += v1.x; acc.y += v1.y; acc.z += v1.z; acc.w += v1.w;
-      acc.x += v2.x; acc.y += v2.y; acc.z += v2.z; acc.w += v2.w;
-      acc.x += v3.x; acc.y += v3.y; acc.z += v3.z; acc.w += v3.w;
-    }
-    for (; g < g1; ++g) {
-      const float4 v = part[(size_t)g * n4 + i];
-      acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
-    }
-  }
-  ps[j][e] = acc;
-  __syncthreads();
-  if (j == 0 && i < n4) {
-    float4 s = ps[0][e];
-#pragma unroll
-    for (int q = 1; q < 8; ++q) {
-      const float4 v = ps[q][e];
-      s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
-    }
-    float4 d = dW[i];
-    d.x += s.x; d.y += s.y; d.z += s.z; d.w += s.w;
-    dW[i] = d;
-  }
-}
-__global__ __launch_bounds__(256) void wgrad_slab_reduce_kernel(int G, size_t n4, const float4* __restrict__ part,
-                                                                float4* __restrict__ dW) {
-  __shared__ float4 ps[8][32];
-  slab_reduce_block(G, n4, part, dW, blockIdx.x, ps);
-}
-// the deferred reductions of a backward in one launch (adp_wgrad_defer / adp_wgrad_flush): segment j takes blocks
-// [blk0[j], blk0[j + 1]), each block the same arithmetic as wgrad_slab_reduce_kernel (bit-identical sums)
-constexpr int SEG_MAX = 32;
-struct SegTable {
-  int n;
-  int blk0[SEG_MAX + 1];
-  int G[SEG_MAX];
-  unsigned long long n4[SEG_MAX];
-  const float4* part[SEG_MAX];
-  float4* dst[SEG_MAX];
-};
-__global__ __launch_bounds__(256) void wgrad_slab_reduce_batched_kernel(SegTable t) {
-  __shared__ float4 ps[8][32];
-  const int b = blockIdx.x;
-  int j = 0;
-  while (j + 1 < t.n && b >= t.blk0[j + 1]) ++j;
-  slab_reduce_block(t.G[j], (size_t)t.n4[j], t.part[j], t.dst[j], b - t.blk0[j], ps);
-}
-
 // Pixel splits: enough blocks to fill the chip (target_blocks), but every split keeps at least
 // min_chunk pixels so that the f32 atomic epilogue (blocks x TN x TK x 4 bytes at ~1.3 TB/s) stays
 // small against the GEMM.
@@ -1885,7 +1820,7 @@ void launch_wcfg(WgradArgs& a, hipStream_t s, int target_blocks, int min_chunk) 
   const bool two = adp::option("tap64_bar", 1) == 2;
   const dim3 grid(tiles * splits), block(WN * WK * 64);
   // split partials: slabs + reduce launch instead of f32 atomics (Kpad == K for every tap64 launch)
-  a.part = nullptr;
+  adp::Slabs part;   // (the handle of a.part, for the reduce)
   const size_t slab = (size_t)a.Nout * a.Kpad;
   // (measured per layer, tools/bench_kernels.py: slabs win 7-14 % on the 256x256 tiles of the >= 256-channel
   // layers, atomics win 4-6 % on the narrow-N tiles, whose slabs are small but split ~1000 ways)
@@ -1893,8 +1828,9 @@ void launch_wcfg(WgradArgs& a, hipStream_t s, int target_blocks, int min_chunk) 
   //  same bits)
   const bool det = adp::option("wgrad_det", 1) != 0;
   if (splits > 1 && (det || adp::option("wgrad_partials", TN >= 256 ? 1 : 0)) && !(ADP_DBG(a) & 1))
-    a.part = det ? adp::reduce_part(0, slab * splits * sizeof(float), s)
-                 : static_cast<float*>(adp::scratch(0, slab * splits * sizeof(float)));
+    part = det ? adp::reduce_part(adp::Slot::WgradPart, slab * splits * sizeof(float), s)
+               : adp::Slabs{(float*)adp::scratch(adp::Slot::WgradPart, slab * splits * sizeof(float), s)};
+  a.part = part.p;
   adp::set_kernel("igemm_wgrad_tap64_kernel<%d, %d, %d, %s, %s>", WN, WK, TNW, two ? "true" : "false",
                   ra ? "true" : "false");
   if (ra && !two) hipLaunchKernelGGL((igemm_wgrad_tap64_kernel<WN, WK, TNW, false, true>), grid, block, 0, s, a);
@@ -1903,7 +1839,7 @@ void launch_wcfg(WgradArgs& a, hipStream_t s, int target_blocks, int min_chunk) 
   else hipLaunchKernelGGL((igemm_wgrad_tap64_kernel<WN, WK, TNW, true, false>), grid, block, 0, s, a);
   adp::kernel_end();   // (the split reduce below is a kernel of its own in rocprofv3's list)
   if (a.part && det) {
-    adp::slab_reduce(splits, slab / 4, a.part, a.dW, s);
+    adp::slab_reduce(splits, slab / 4, part, a.dW, s);
   } else if (a.part) {
     const size_t n4 = slab / 4;
     const int groups = (splits + WG_SG - 1) / WG_SG;
@@ -1917,155 +1853,6 @@ void launch_wcfg(WgradArgs& a, hipStream_t s, int target_blocks, int min_chunk) 
 }  // namespace
 
 namespace adp {
-// ---- deferred slab reductions (adp_wgrad_defer / adp_wgrad_flush). Every deterministic weight / bias gradient launch
-// is followed by a small reduce launch (~10 us) and, like every launch, a ~5.8 us dependency gap: 21 per training
-// step, ~0.34 ms (profiles/r05a: tools/kstats.py, gap analysis in DESIGN.md §3 (30)). Deferred, the slabs go to a
-// per-stream arena (chunks kept across steps) and the reductions are recorded; adp_wgrad_flush launches them all as one
-// kernel (up to SEG_MAX segments per launch), in the same fixed order: bit-identical gradients.
-struct Deferred {
-  bool on = false;
-  bool fallback = false;                            // the last reduce_part came from scratch: reduce it at once
-  std::vector<std::pair<char*, size_t>> chunks;   // (base, bytes) on the key's device, reused across steps
-  size_t ci = 0, used = 0;                          // current chunk, bytes used in it
-  size_t pending = 0;                               // slab bytes recorded since the last launch of the tables
-  std::vector<SegTable> tables;                     // (built as the segments are recorded)
-};
-static void launch_tables(std::vector<SegTable>& tables, hipStream_t s) {
-  for (const SegTable& t : tables)
-    if (t.n > 0) hipLaunchKernelGGL(wgrad_slab_reduce_batched_kernel, dim3((unsigned)t.blk0[t.n]), dim3(256), 0, s, t);
-  tables.clear();
-}
-// keyed by (device, stream) like every other piece of library state (round-5 ADVICE): the default stream is handle 0
-// on every device, and an arena chunk must live on the device whose launches write it
-using DefKey = std::pair<int, hipStream_t>;
-static std::mutex g_def_mu;
-static std::map<DefKey, Deferred>& deferred_map() {
-  static std::map<DefKey, Deferred> m;
-  return m;
-}
-static DefKey def_key(hipStream_t s) {
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  return {dev, s};
-}
-float* reduce_part(int slot, size_t bytes, hipStream_t s) {
-  {
-    std::lock_guard<std::mutex> lk(g_def_mu);
-    auto it = deferred_map().find(def_key(s));
-    if (it != deferred_map().end() && it->second.on) {
-      Deferred& d = it->second;
-      d.fallback = false;
-      bytes = (bytes + 255) / 256 * 256;
-      // (option wgrad_defer_mb: once the recorded slabs would pass this many MB, the recorded reductions are
-      //  launched first and the arena starts over: the slabs are re-read while they still sit in the MALL, and the
-      //  arena's first chunk stays resident)
-      const size_t lim = (size_t)std::max(0, option("wgrad_defer_mb", 64)) << 20;
-      if (lim && d.pending + bytes > lim && !d.tables.empty()) {
-        launch_tables(d.tables, s);
-        d.ci = 0;
-        d.used = 0;
-        d.pending = 0;
-      }
-      while (d.ci < d.chunks.size() && d.used + bytes > d.chunks[d.ci].second) { ++d.ci; d.used = 0; }
-      if (d.ci == d.chunks.size()) {   // (first steps only: a new chunk, kept until adp_wgrad_release)
-        const size_t sz = std::max(bytes, (size_t)256 << 20);
-        void* p = nullptr;
-        if (hipMalloc(&p, sz) != hipSuccess) {
-          // no arena: this launch's slabs go to the scratch slot and its reduction runs at once (slab_reduce), still
-          // in a fixed order (round-5 ADVICE: it fell back to the f32 atomics and left a stale error)
-          (void)hipGetLastError();
-          d.fallback = true;
-          return static_cast<float*>(scratch(slot, bytes));
-        }
-        d.chunks.push_back({static_cast<char*>(p), sz});
-        d.used = 0;
-      }
-      d.pending += bytes;
-      float* r = reinterpret_cast<float*>(d.chunks[d.ci].first + d.used);
-      d.used += bytes;
-      return r;
-    }
-  }
-  return static_cast<float*>(scratch(slot, bytes));
-}
-void slab_reduce(int G, size_t n4, const float* part, float* dst, hipStream_t s) {
-  {
-    std::lock_guard<std::mutex> lk(g_def_mu);
-    auto it = deferred_map().find(def_key(s));
-    if (it != deferred_map().end() && it->second.on && !it->second.fallback) {
-      Deferred& d = it->second;
-      // segments of one launch run concurrently: a destination already in the open table (the same gradient
-      // accumulated twice) starts a new table, launched after it
-      bool clash = false;
-      if (!d.tables.empty()) {
-        const SegTable& o = d.tables.back();
-        const float4* lo = reinterpret_cast<const float4*>(dst);
-        for (int j = 0; j < o.n && !clash; ++j) clash = lo < o.dst[j] + o.n4[j] && o.dst[j] < lo + n4;
-      }
-      if (d.tables.empty() || d.tables.back().n == SEG_MAX || clash) {
-        d.tables.emplace_back();
-        d.tables.back().n = 0;
-        d.tables.back().blk0[0] = 0;
-      }
-      SegTable& t = d.tables.back();
-      const int j = t.n++;
-      t.G[j] = G;
-      t.n4[j] = n4;
-      t.part[j] = reinterpret_cast<const float4*>(part);
-      t.dst[j] = reinterpret_cast<float4*>(dst);
-      t.blk0[j + 1] = t.blk0[j] + (int)((n4 + 31) / 32);
-      return;
-    }
-    if (it != deferred_map().end()) it->second.fallback = false;
-  }
-  hipLaunchKernelGGL(wgrad_slab_reduce_kernel, dim3((unsigned)((n4 + 31) / 32)), dim3(256), 0, s, G, n4,
-                     reinterpret_cast<const float4*>(part), reinterpret_cast<float4*>(dst));
-}
-int wgrad_defer(hipStream_t s, int on) {
-  std::lock_guard<std::mutex> lk(g_def_mu);
-  Deferred& d = deferred_map()[def_key(s)];
-  if (!on && !d.tables.empty()) { set_error("adp_wgrad_defer: reductions pending (adp_wgrad_flush first)"); return -1; }
-  d.on = on != 0 && option("wgrad_defer", 1);   // (option wgrad_defer = 0: every reduction launched at once)
-  return 0;
-}
-// launch the pending reductions of stream s (stream-ordered after the launches that wrote their slabs) and end the
-// deferral; the arena is reused by the next deferred launches, which are ordered after these reductions
-int wgrad_flush(hipStream_t s) {
-  std::vector<SegTable> tables;
-  {
-    std::lock_guard<std::mutex> lk(g_def_mu);
-    Deferred& d = deferred_map()[def_key(s)];
-    tables.swap(d.tables);
-    d.on = false;
-    d.ci = 0;
-    d.used = 0;
-    d.pending = 0;
-  }
-  launch_tables(tables, s);
-  return 0;
-}
-// free the arena of (current device, stream s) and forget the stream (an arena per stream that ever
-// deferred, never freed; a destroyed stream's reused handle inherited it). Synchronises s first; an error with
-// reductions pending (flush first).
-int wgrad_release(hipStream_t s) {
-  std::lock_guard<std::mutex> lk(g_def_mu);
-  auto it = deferred_map().find(def_key(s));
-  if (it == deferred_map().end()) return 0;
-  if (!it->second.tables.empty()) { set_error("adp_wgrad_release: reductions pending (adp_wgrad_flush first)"); return -1; }
-  if (!it->second.chunks.empty() && hipStreamSynchronize(s) != hipSuccess) {
-    set_error("adp_wgrad_release: stream synchronisation failed");
-    return -1;
-  }
-  for (auto& c : it->second.chunks) (void)hipFree(c.first);
-  deferred_map().erase(it);
-  return 0;
-}
-// (test hook) the number of arena chunks of (current device, stream s)
-int wgrad_arena_chunks(hipStream_t s) {
-  std::lock_guard<std::mutex> lk(g_def_mu);
-  auto it = deferred_map().find(def_key(s));
-  return it == deferred_map().end() ? 0 : (int)it->second.chunks.size();
-}
 // shapes of the persistent halo weight-gradient kernel
 static bool halop_ok(const WgradArgs& a) {
   const int cin = a.CAs + a.CBs;
@@ -2108,8 +1895,9 @@ int launch_wgrad_tap64(WgradArgs& a, hipStream_t s) {
     const int tiles = a.Nimg * (a.Ho / 8) * (a.Wo / 32);
     const int grid = std::max(1, std::min(tiles, option("wgrad_cin8_grid", 256)));
     // wgrad_det (default on): per-block slabs [grid][64][Kpad] + the fixed-order reduce instead of f32 atomics
-    a.part = option("wgrad_det", 1) && !(ADP_DBG(a) & 1)
-                 ? reduce_part(0, (size_t)grid * 64 * a.Kpad * sizeof(float), s) : nullptr;
+    const Slabs part = option("wgrad_det", 1) && !(ADP_DBG(a) & 1)
+                           ? reduce_part(Slot::WgradPart, (size_t)grid * 64 * a.Kpad * sizeof(float), s) : Slabs{};
+    a.part = part.p;
     if (a.bna_dA) {
       adp::set_kernel("igemm_wgrad_cin8_kernel<true>");
       hipLaunchKernelGGL((igemm_wgrad_cin8_kernel<true>), dim3(grid), dim3(512), 0, s, a);
@@ -2119,7 +1907,7 @@ int launch_wgrad_tap64(WgradArgs& a, hipStream_t s) {
     }
     if (a.part) {
       adp::kernel_end();
-      slab_reduce(grid, (size_t)64 * a.Kpad / 4, a.part, a.dW, s);
+      slab_reduce(grid, (size_t)64 * a.Kpad / 4, part, a.dW, s);
       a.part = nullptr;
     }
     return 1;
@@ -2141,11 +1929,12 @@ int launch_wgrad_tap64(WgradArgs& a, hipStream_t s) {
     // output form (option wgrad_det, default on): static lists write per-block slabs summed in a fixed order by
     // wgrad_slab_reduce_kernel (one block per combination: dW += partial in place), so two runs give the same bits;
     // wgrad_det = 0 or claimed patches: f32 atomics in the order blocks finish
-    a.part = nullptr;
+    Slabs part;
     a.part_rmw = 0;
     const bool det = !a.claim && option("wgrad_det", 1) && !(ADP_DBG(a) & 1);
     if (det && per == 1 && ((uintptr_t)a.dW & 15) == 0) a.part_rmw = 1;   // (16-B pieces of dW: aligned dW only)
-    else if (det) a.part = reduce_part(0, (size_t)per * a.Nout * a.Kpad * sizeof(float), s);
+    else if (det) part = reduce_part(Slot::WgradPart, (size_t)per * a.Nout * a.Kpad * sizeof(float), s);
+    a.part = part.p;
     // (a failed scratch allocation leaves part null: the atomic form)
     if (a.bna_dA) {   // the caller checked wgrad_bna_fusable
       if (option("wgrad_halop_spread", 4) == 8) {
@@ -2208,7 +1997,7 @@ int launch_wgrad_tap64(WgradArgs& a, hipStream_t s) {
     }
     if (a.part) {   // (a kernel of its own in rocprofv3's list and outside the conv's event bracket)
       adp::kernel_end();
-      slab_reduce(per, (size_t)a.Nout * a.Kpad / 4, a.part, a.dW, s);
+      slab_reduce(per, (size_t)a.Nout * a.Kpad / 4, part, a.dW, s);
       a.part = nullptr;
     }
     return 1;

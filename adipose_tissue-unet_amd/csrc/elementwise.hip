@@ -5,10 +5,8 @@
 //   UpSampling2D((2,2)) gradient            :691,698,705
 //   Adam / AdamW (Keras defaults)           :800-806
 //   EMACallback update (ema = d*ema+(1-d)w) :455-459
-#include "common.h"
+#include "workspace.h"
 #include "../../include/adipose_hip.h"
-#include <map>
-#include <mutex>
 
 namespace {
 
@@ -833,121 +831,6 @@ __global__ void ema_kernel(size_t n, float* ema, const float* p, float d) {
 }  // namespace
 
 namespace adp {
-// a conv launch with bn_defer_fold leaves its BatchNorm sums in the replicas; until the matching
-// adp_bn_finalize_fold (same channel count, sum vector and stream) runs, no other launch may use them
-struct PendingFold { bool on = false; int C = 0; const float* sum = nullptr; hipStream_t s = nullptr; };
-static std::mutex g_fold_mu;
-static std::map<int, PendingFold>& pending_folds() {
-  static std::map<int, PendingFold> m;
-  return m;
-}
-int defer_fold_begin(int C, const float* sum, hipStream_t s) {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) { set_error("defer_fold: hipGetDevice failed"); return -2; }
-  std::lock_guard<std::mutex> lk(g_fold_mu);
-  pending_folds()[dev] = PendingFold{true, C, sum, s};
-  return 0;
-}
-static double* stat_scratch_impl(bool fold, int C, const float* sum, hipStream_t s) {
-  static std::mutex mu;
-  static std::map<int, double*> per_dev;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) { set_error("stat_scratch: hipGetDevice failed"); return nullptr; }
-  {
-    std::lock_guard<std::mutex> lk(g_fold_mu);
-    PendingFold& pf = pending_folds()[dev];
-    if (fold) {
-      if (!pf.on || pf.C != C || pf.sum != sum || pf.s != s) {
-        set_error(pf.on ? "adp_bn_finalize_fold: does not match the pending deferred fold (channel count, sum "
-                          "vector or stream differ)"
-                        : "adp_bn_finalize_fold: no conv launch with bn_defer_fold is pending");
-        return nullptr;
-      }
-      pf.on = false;
-    } else if (pf.on) {
-      set_error("BatchNorm accumulator replicas hold the sums of a bn_defer_fold launch: adp_bn_finalize_fold "
-                "must run first");
-      return nullptr;
-    }
-  }
-  std::lock_guard<std::mutex> lk(mu);
-  auto it = per_dev.find(dev);
-  if (it != per_dev.end()) return it->second;
-  const size_t bytes = sizeof(double) * STAT_REPL * 2 * STAT_CMAX;
-  double* p = nullptr;
-  if (hipMalloc(&p, bytes) != hipSuccess || hipMemset(p, 0, bytes) != hipSuccess ||
-      hipDeviceSynchronize() != hipSuccess) {
-    set_error("stat_scratch: allocation of the BatchNorm accumulator replicas failed");
-    return nullptr;
-  }
-  per_dev[dev] = p;
-  return p;
-}
-double* stat_scratch() { return stat_scratch_impl(false, 0, nullptr, nullptr); }
-// drop a deferred fold that never reached its adp_bn_finalize_fold (an error or exception between the two) and
-// re-zero the replicas it left its sums in, stream-ordered on s; a no-op when nothing is pending -- and when the
-// pending fold was left on another stream: that one belongs to another caller (engine handle, thread) whose launch
-// may still be in flight, and a memset on s would neither be ordered after it nor be ours to make (round-4 ADVICE)
-int bn_fold_reset(hipStream_t s) {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) { set_error("adp_bn_fold_reset: hipGetDevice failed"); return -2; }
-  {
-    std::lock_guard<std::mutex> lk(g_fold_mu);
-    PendingFold& pf = pending_folds()[dev];
-    if (!pf.on || pf.s != s) return 0;
-    pf.on = false;
-  }
-  double* p = stat_scratch();
-  if (!p) return -2;
-  if (hipMemsetAsync(p, 0, sizeof(double) * STAT_REPL * 2 * STAT_CMAX, s) != hipSuccess) {
-    set_error("adp_bn_fold_reset: clearing the accumulator replicas failed");
-    return -2;
-  }
-  return 0;
-}
-double* stat_scratch_fold(int C, const float* sum, hipStream_t s) { return stat_scratch_impl(true, C, sum, s); }
-int* claim_slot() {
-  static std::mutex mu;
-  static std::map<int, std::pair<int*, unsigned>> per_dev;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) { set_error("claim_slot: hipGetDevice failed"); return nullptr; }
-  std::lock_guard<std::mutex> lk(mu);
-  auto& e = per_dev[dev];
-  if (!e.first) {
-    const size_t bytes = sizeof(int) * CLAIM_SLOTS * CLAIM_INTS;
-    if (hipMalloc(&e.first, bytes) != hipSuccess || hipMemset(e.first, 0, bytes) != hipSuccess ||
-        hipDeviceSynchronize() != hipSuccess) {
-      e.first = nullptr;
-      set_error("claim_slot: allocation of the tile-claiming counters failed");
-      return nullptr;
-    }
-  }
-  return e.first + (size_t)(e.second++ % CLAIM_SLOTS) * CLAIM_INTS;
-}
-void* scratch(int slot, size_t bytes) {
-  static std::mutex mu;
-  static std::map<std::pair<int, int>, std::pair<void*, size_t>> bufs;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) { set_error("scratch: hipGetDevice failed"); return nullptr; }
-  std::lock_guard<std::mutex> lk(mu);
-  auto& e = bufs[{dev, slot}];
-  if (e.second >= bytes) return e.first;
-  if (e.first) {   // kernels queued on any stream may still use the old buffer
-    if (hipDeviceSynchronize() != hipSuccess || hipFree(e.first) != hipSuccess) {
-      set_error("scratch: releasing the old buffer failed");
-      return nullptr;
-    }
-    e = {nullptr, 0};
-  }
-  const size_t want = bytes + bytes / 4;   // grow with headroom
-  if (hipMalloc(&e.first, want) != hipSuccess) {
-    e = {nullptr, 0};
-    set_error("scratch: hipMalloc failed");
-    return nullptr;
-  }
-  e.second = want;
-  return e.first;
-}
 int stat_fold(int C, float* dst0, float* dst1, hipStream_t s) { return stat_fold_at(0, C, dst0, dst1, s); }
 int stat_fold_at(int c0, int C, float* dst0, float* dst1, hipStream_t s) {
   double* sc = stat_scratch();

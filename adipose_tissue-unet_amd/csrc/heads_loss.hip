@@ -7,7 +7,7 @@
 //              (clip to [1e-7, 1-1e-7], log(p+1e-7), mean over the last axis)
 //   metrics    dice_coef src/utils/model.py:93-98, Keras binary_accuracy (threshold 0.5),
 //              calculate_pixel_metrics counts Segmentation/full_evaluation_enhanced.py:721-785
-#include "common.h"
+#include "workspace.h"
 #include <algorithm>
 #include "../../include/adipose_hip.h"
 

@@ -14,7 +14,7 @@
 //   3. NaN when only one class is present (the reference's early return).
 #include <hipcub/hipcub.hpp>
 
-#include "common.h"
+#include "workspace.h"
 #include "../../include/adipose_hip.h"
 
 #define CL_OK(x)              \
@@ -94,7 +94,7 @@ extern "C" int adp_auc_metrics(size_t n, const float* pred, const float* truth, 
               "adp_auc_metrics: temporary-storage query failed");
   const size_t tmp_b = (std::max(sort_b, std::max(sum_b, max_b)) + 255) / 256 * 256;
   const size_t arr = (n * 4 + 255) / 256 * 256;
-  char* w = static_cast<char*>(adp::scratch(2, 6 * arr + tmp_b + 256));
+  char* w = static_cast<char*>(adp::scratch(adp::Slot::AucSort, 6 * arr + tmp_b + 256, s));
   if (!w) return -2;
   uint32_t* key_in = reinterpret_cast<uint32_t*>(w);
   uint32_t* key_out = reinterpret_cast<uint32_t*>(w + arr);
@@ -244,7 +244,8 @@ extern "C" int adp_distance_transform(int H, int W, const float* src, float thr,
   ADP_REQUIRE(H > 0 && W > 0 && src && dist && sy > 0 && sx > 0, "adp_distance_transform: bad arguments");
   hipStream_t s = (hipStream_t)st;
   const size_t n = (size_t)H * W;
-  char* w = static_cast<char*>(adp::scratch(3, n * 8 + n * 4 + (size_t)H * (W + 1) * 8 + 512));
+  const size_t bytes = n * 8 + n * 4 + (size_t)H * (W + 1) * 8 + 512;
+  char* w = static_cast<char*>(adp::scratch(adp::Slot::DistField, bytes, s));
   if (!w) return -2;
   double* g = reinterpret_cast<double*>(w);
   double* z = reinterpret_cast<double*>(w + n * 8);
@@ -259,8 +260,8 @@ extern "C" int adp_boundary_metrics(int H, int W, const float* pred, const float
   ADP_REQUIRE(H > 0 && W > 0 && pred && truth && out && sy > 0 && sx > 0, "adp_boundary_metrics: bad arguments");
   hipStream_t s = (hipStream_t)st;
   const size_t n = (size_t)H * W;
-  // own workspace (slot 4): dt_pred, dt_true, samples (<= 2n), counters; the EDTs use slot 3
-  char* w = static_cast<char*>(adp::scratch(4, 4 * n * 8 + 512));
+  // own workspace: dt_pred, dt_true, samples (<= 2n), counters; the EDTs use Slot::DistField
+  char* w = static_cast<char*>(adp::scratch(adp::Slot::BoundaryDist, 4 * n * 8 + 512, s));
   if (!w) return -2;
   double* dtp = reinterpret_cast<double*>(w);
   double* dtt = dtp + n;
@@ -282,7 +283,7 @@ extern "C" int adp_boundary_metrics(int H, int W, const float* pred, const float
   size_t sort_b = 0;
   ADP_REQUIRE(hipcub::DeviceRadixSort::SortKeys(nullptr, sort_b, (double*)nullptr, (double*)nullptr, (int)m, 0, 64, s) ==
                   hipSuccess, "adp_boundary_metrics: sort query failed");
-  char* w2 = static_cast<char*>(adp::scratch(5, m * 8 + sort_b + 512));
+  char* w2 = static_cast<char*>(adp::scratch(adp::Slot::BoundarySort, m * 8 + sort_b + 512, s));
   if (!w2) return -2;
   double* sorted = reinterpret_cast<double*>(w2);
   void* tmp = w2 + (m * 8 + 255) / 256 * 256;

@@ -526,8 +526,9 @@ def get_option(name):
 
 
 def wgrad_release(stream=None):
-    """adp_wgrad_release: free the deferral arena of (current device, stream) and forget the stream (synchronises it;
-    AdpError with reductions pending). stream: a torch.cuda.Stream, default the current one."""
+    """adp_wgrad_release: free the library's workspace of (current device, stream), deferral arena and scratch, and
+    forget the stream (synchronises it; AdpError with reductions pending). stream: a torch.cuda.Stream, default the
+    current one."""
     call("adp_wgrad_release", stream_ptr() if stream is None else stream.cuda_stream)
 
 

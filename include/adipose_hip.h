@@ -10,7 +10,12 @@
  *   - Every call returns 0 on success, <0 on error; adp_last_error() returns a thread-local message.
  *   - Pointers are DEVICE pointers unless stated; the caller owns every buffer.
  *   - Calls are asynchronous on the given hipStream_t (passed as void* so the header needs no HIP
- *     include) and never allocate, free or synchronise (safe to capture in a hipGraph).
+ *     include). The library keeps a device workspace of its own: per device the BatchNorm accumulator
+ *     replicas and the tile-claim counters, per (device, stream) scratch buffers and the deferral arena.
+ *     The first use of a device or of a (device, stream) allocates, and so does a launch that needs more
+ *     scratch or arena than the stream holds (growing scratch synchronises the device and frees the old
+ *     buffer); no other call allocates, frees or synchronises, so a launch sequence that has run once
+ *     on a stream can be captured in a hipGraph. adp_wgrad_release frees a stream's workspace.
  *   - dtype: ADP_DTYPE_F32 (parity path, exact f32 MFMA) or ADP_DTYPE_BF16 (throughput path,
  *     f32 accumulation); ADP_DTYPE_FP8 (e4m3fn operands, block-scaled MFMA, f32 accumulation) for
  *     forward-only launches (BASELINE.json configs[4]). Activations are NHWC with channel stride a
@@ -78,7 +83,10 @@ typedef struct adp_conv_desc {
                                columns of the pad channels [real, stride) are zeros (packed layers) */
   int Nout_real;            /* v19, optional (0 = unknown): real GEMM columns when weight rows [real, Nout)
                                are zeros. With these hints a kernel may skip products with zero weights
-                               (f32 44-channel layers in 64-channel strides); results are unchanged */
+                               (f32 44-channel layers in 64-channel strides); results are unchanged.
+                               Weight-gradient launches: the hints also require the pad channels of the
+                               sources and of dY to be zeros, and the gradient of the pad rows and columns
+                               is not accumulated */
 } adp_conv_desc;
 
 typedef struct adp_conv_io {
@@ -133,10 +141,14 @@ const char* adp_source_hash(void);
  * epilogue store width (round 3, bit-identical either way): "tap64p_wide" (1), "tap64p_wide_f8" (0), "halop_wide"
  * (0 off, 1 tile-serial forms, 2 all, 3 default: all but the pipelined statistics forms), "cin8_wide" (1);
  * "wgrad_cin8_bna" (1: the input layer's fused BN-backward weight gradient when dY = NULL), "tap64_kpipe" (0:
- * mid-step barrier in the tap64 K loop); "wgrad_debug" / "fwd_debug" are timing-only ablations (results invalid). */
+ * mid-step barrier in the tap64 K loop); "wgrad_debug" / "fwd_debug" are timing-only ablations (results invalid).
+ * "wgrad_arena_max_kb" (0 = no limit, default): the most KiB a stream's deferral arena may hold in total; a new chunk
+ * is max(request, min(256 MiB, what is left under the limit)), and a request that would pass the limit takes its slabs
+ * from scratch and is reduced at once, as after a failed allocation (same bits). */
 int adp_set_option(const char* name, int value);
-/* The value adp_set_option gave `name`, INT_MIN when unset (v20; "tap64_ksplit_last" reports the split-K factor of the
- * last tap64 launch: 0 = none). */
+/* The value adp_set_option gave `name`, INT_MIN when unset (v20). "tap64_ksplit_last" is a report, not an option: the
+ * split-K factor of the calling thread's last tap64 forward launch (0 = unsplit, INT_MIN before the first); setting it
+ * is an error. */
 int adp_get_option(const char* name);
 /* Per-launch timing of the conv kernels (bench roofline; no reference counterpart). mode 1: clear the record
  * and start recording a HIP event pair around the MAIN kernel of every adp_conv_fwd / adp_conv_wgrad(_bn)
@@ -258,9 +270,11 @@ int adp_bn_fold_reset(adp_stream_t s);
  * them (the optimizer, a gradient all-reduce). adp_wgrad_defer(0, s) with reductions pending is an error. */
 int adp_wgrad_defer(int on, adp_stream_t s);
 int adp_wgrad_flush(adp_stream_t s);
-/* The deferral arena of (current device, stream s) -- chunks of >= 256 MiB allocated by the first deferred steps and reused
- * afterwards -- freed, and the stream forgotten (v20). Synchronises s; an error with reductions pending. Call it before
- * destroying a stream that deferred. adp_wgrad_arena_chunks: the number of arena chunks of (device, s) (test hook). */
+/* Frees the whole workspace of (current device, stream s) and forgets the stream (v20): the deferral arena -- chunks of
+ * 256 MiB or the request if larger (option "wgrad_arena_max_kb" limits them), allocated by the first deferred steps and
+ * reused afterwards -- and the stream's scratch buffers. Synchronises s if it holds anything; an error with reductions
+ * pending. Call it before destroying a stream the library has launched on. adp_wgrad_arena_chunks: the number of arena
+ * chunks of (device, s) (test hook). */
 int adp_wgrad_release(adp_stream_t s);
 int adp_wgrad_arena_chunks(adp_stream_t s);
 /* a = relu(z*scale + shift), the post-BatchNorm activation, materialised once per layer */

@@ -269,7 +269,7 @@ def test_unet_bn_fallback_paths_match_default(flag):
     """The alternate schedules nets.UNetBN keeps for A/B runs (each fusion flag off, and the pool backward's
     argmax read from the stored activation instead of recomputed from z) give the default path's outputs and
     gradients (bf16, base 64, so every fused kernel form is the one the bench runs). Since round 4 the BatchNorm
-    sums are deterministic (f64 replicas fed fixed-order f32 partials, csrc/common.h) and every fused form computes
+    sums are deterministic (f64 replicas fed fixed-order f32 partials, csrc/workspace.h) and every fused form computes
     the same f32 partials as its unfused pair, so the outputs are bit-identical (measured: max difference 0 for
     every flag, profiles/r04c_gates.log; round 3 allowed 1.5e-2 and gradient cosines down to 0.98, when f32
     atomics in run order made even two runs of one path differ). Weight gradients within 1e-5 (the fused and unfused
@@ -304,7 +304,7 @@ def test_unet_bn_fallback_paths_match_default(flag):
 def test_unet_bn_bf16_runs_are_deterministic(levels, S):
     """Two identical bf16 training forward + backward passes give bit-identical outputs, BatchNorm statistics and
     data-gradient chains: since round 4 the BatchNorm sums (forward statistics in every conv epilogue and the
-    fused BN-backward reductions) are f64 replicas fed f32 partials of a fixed order (csrc/common.h), where f32
+    fused BN-backward reductions) are f64 replicas fed f32 partials of a fixed order (csrc/workspace.h), where f32
     atomics in run-dependent order used to make runs differ by bf16 rounding flips (per-layer gradient cosines down
     to 0.9895: profiles/r03_bf16_bn_nondeterminism.txt). Since round 5 the weight gradients are bit-identical too:
     the halo / input-layer / tap64 weight-gradient kernels write per-block slabs that a fixed-order reduce adds into

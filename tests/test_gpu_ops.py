@@ -1757,6 +1757,53 @@ def test_wgrad_deferred_reductions():
     assert torch.equal(d, ref_h)
 
 
+@pytest.mark.parametrize("cap_kb", [1536, 64], ids=["weights_in_arena", "bias_in_arena"])
+def test_wgrad_defer_mixed_arena_and_scratch(cap_kb):
+    """One deferred launch whose two slab buffers land on different sides of the arena cap (option wgrad_arena_max_kb):
+    the f32 one-channel input layer takes weight slabs (G = M / 32 = 64 slabs of 64 x 96 f32 = 1536 KiB) and bias rows
+    (64 x 64 f32 = 16 KiB) before it reduces either. The buffer in the arena is recorded and reduced by the flush, the
+    one in scratch is reduced at once -- each by its own handle, whichever came second -- and a second launch whose
+    fallback reuses the same scratch does not disturb the first: all four gradients are the immediate-mode bits. The
+    written / untouched pattern after the first launch is what shows that the mixed case was reached."""
+    N, H, W_, nst = 2, 32, 32, 64
+    g = torch.Generator().manual_seed(137)
+    pairs = []
+    for _ in range(2):
+        x = torch.zeros(N, H, W_, 8)
+        x[..., 0] = torch.randn(N, H, W_, generator=g)
+        pairs.append((x.to(DEV), torch.randn(N, H, W_, nst, generator=g).to(DEV)))
+
+    def launch(x, dy):
+        dW, dB = torch.zeros(nst, 96, device=DEV), torch.zeros(nst, device=DEV)
+        ops.conv_wgrad(x, dy, dW, nst, dB=dB, real=(1, 0, nst))
+        return dW, dB
+
+    refs = [launch(*p) for p in pairs]
+    torch.cuda.synchronize()
+    ops.wgrad_release()   # (an arena an earlier test left on this stream would count against the cap)
+    ops.set_option("wgrad_arena_max_kb", cap_kb)
+    try:
+        ops.wgrad_defer(True)
+        try:
+            dW1, dB1 = launch(*pairs[0])
+            torch.cuda.synchronize()
+            kname = _lib.lib().adp_last_kernel().decode()
+            untouched = [bool((t == 0).all()) for t in (dW1, dB1)]
+            dW2, dB2 = launch(*pairs[1])
+        finally:
+            ops.wgrad_flush()
+        torch.cuda.synchronize()
+        chunks = ops.wgrad_arena_chunks()
+    finally:
+        ops.set_option("wgrad_arena_max_kb", None)
+        ops.wgrad_release()
+    assert kname == "wgrad_in1_f32_kernel", kname
+    assert untouched == ([True, False] if cap_kb == 1536 else [False, True]), untouched
+    for got, ref in zip((dW1, dB1, dW2, dB2), refs[0] + refs[1]):
+        assert torch.equal(got, ref)
+    assert chunks == 1
+
+
 F32_HALO_WGRAD_CASES = [
     # name, N, H, W (output grid), source channel strides, Nout, up
     ("c64_64", 2, 32, 64, [64], 64, False),
@@ -2683,3 +2730,95 @@ def test_tap64_split_k(dt, epi, dil, hw):
         wk = Wm.view(cout, 3, 3, cin).permute(0, 3, 1, 2)
         ref = torch.nn.functional.conv2d(x.permute(0, 3, 1, 2), wk, bias.cpu(), padding=dil, dilation=dil).relu()
         assert relerr(o1, ref.permute(0, 2, 3, 1)) < 1e-4
+
+
+def _split_k_case(seed):
+    """Operands of test_tap64_split_k's f32 hw = 32 shape (N = 2, 32 x 32, 352 -> 352): 48 tiles, split over K."""
+    N, hw, c = 2, 32, 352
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn(N, hw, hw, c, generator=g).to(DEV)
+    Wm = torch.randn(c, 9 * c, generator=g) * (1.0 / math.sqrt(9 * c))
+    Wd = torch.cat([Wm, torch.zeros((c + 63) // 64 * 64 - c, 9 * c)]).to(DEV)
+    return x, Wd, c
+
+
+def test_workspace_scratch_is_per_stream():
+    """Library scratch is keyed by (device, stream): launches on two streams of one device that use the same kind of
+    temporary -- the split-K partial tiles of the tap64 forward, then the slabs of the immediate-mode deterministic
+    weight gradient -- each give the bits their stream's inputs give alone. The two streams are likely but not
+    guaranteed to overlap, so a pass does not prove the keying (that is checked by reading csrc/workspace.hip); the
+    test is a cheap regression net for it."""
+    cur = torch.cuda.current_stream()
+    streams = [torch.cuda.Stream(device=DEV), torch.cuda.Stream(device=DEV)]
+    rounds = 8
+
+    def both_legs(launch, zeros):
+        """launch(i, out) runs stream i's problem into out: alone first (the reference), then `rounds` launches
+        alternating between the streams with no synchronisation in between."""
+        refs = [zeros(), zeros()]
+        outs = [[zeros() for _ in range(rounds)] for _ in streams]
+        for i, st in enumerate(streams):
+            st.wait_stream(cur)
+            with torch.cuda.stream(st):
+                launch(i, refs[i])
+            torch.cuda.synchronize()
+        for r in range(rounds):
+            for i, st in enumerate(streams):
+                with torch.cuda.stream(st):
+                    launch(i, outs[i][r])
+        torch.cuda.synchronize()
+        for i in range(len(streams)):
+            for r in range(rounds):
+                assert torch.equal(outs[i][r], refs[i]), (i, r)
+        assert not torch.equal(refs[0], refs[1])
+
+    try:
+        # leg 1: split-K forward
+        fwd = [_split_k_case(73), _split_k_case(74)]
+        splits = []
+
+        def launch_fwd(i, out):
+            x, Wd, c = fwd[i]
+            ops.conv_fwd(x, Wd, c, out=out)
+            splits.append(ops.get_option("tap64_ksplit_last"))
+
+        ops.set_option("tap64_ksplit", 1)
+        try:
+            both_legs(launch_fwd, lambda: torch.zeros(2, 32, 32, 352, device=DEV))
+        finally:
+            ops.set_option("tap64_ksplit", 0)
+        assert min(splits) >= 2, splits
+        # leg 2: immediate-mode deterministic weight gradient (bf16, N = 2, 64 x 64, 64 -> 64)
+        _, _, _, l = make_case(2, 64, [64], 64, 1, False, seed=25)
+        g = torch.Generator().manual_seed(75)
+        wg = [(torch.randn(2, 64, 64, 64, generator=g).to(DEV, torch.bfloat16),
+               nhwc_pad(rb(torch.randn(2, 64, 64, 64, generator=g), torch.bfloat16), l.cout_s, torch.bfloat16))
+              for _ in streams]
+        both_legs(lambda i, out: ops.conv_wgrad(wg[i][0], wg[i][1], out, l.Nout),
+                  lambda: torch.zeros((l.Npad, l.Kpad), device=DEV))
+    finally:
+        torch.cuda.synchronize()
+        for st in streams:
+            ops.wgrad_release(st)
+
+
+def test_ksplit_report_is_not_an_option():
+    """"tap64_ksplit_last" is the library's report of the last tap64 launch's split-K factor, read with get_option; it
+    is not part of the option map: setting it is an error and leaves the report as it was, and an unsplit launch
+    reports 0."""
+    x, Wd, c = _split_k_case(76)
+    out = torch.zeros(2, 32, 32, 352, device=DEV)
+    ops.set_option("tap64_ksplit", 1)
+    try:
+        ops.conv_fwd(x, Wd, c, out=out)
+    finally:
+        ops.set_option("tap64_ksplit", 0)
+    ks = ops.get_option("tap64_ksplit_last")
+    assert ks >= 2, ks
+    with pytest.raises(ops.AdpError):
+        ops.set_option("tap64_ksplit_last", 5)
+    assert ops.get_option("tap64_ksplit_last") == ks
+    ops.conv_fwd(x, Wd, c, out=out)   # (tap64_ksplit = 0: unsplit)
+    assert _lib.lib().adp_last_kernel().decode().startswith("igemm_fwd_tap64_kernel")
+    assert ops.get_option("tap64_ksplit_last") == 0
+    torch.cuda.synchronize()
