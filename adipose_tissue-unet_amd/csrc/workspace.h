@@ -38,6 +38,7 @@ enum class Slot {
   DistField,     // adp_distance_transform: the two passes' fields
   BoundaryDist,  // adp_boundary_metrics: the four distance fields
   BoundarySort,  // adp_boundary_metrics: surface distances and the sort's temporary
+  StainPart,     // adp_stain_lab_stats: one row of six f64 sums per block
   Count
 };
 void* scratch(Slot slot, size_t bytes, hipStream_t s);

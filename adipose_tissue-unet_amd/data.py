@@ -212,6 +212,14 @@ def read_gray(path):
         return np.asarray(im.convert("L"), np.float32)
 
 
+def read_rgb(path):
+    """np.array(Image.open(path)) as the stain normaliser takes it -> uint8 (H, W, 3)."""
+    from PIL import Image
+
+    with Image.open(path) as im:
+        return np.asarray(im.convert("RGB"), np.uint8)
+
+
 def read_mask(path):
     from PIL import Image
 

@@ -16,6 +16,10 @@ group, sliding-window positions are sharded by contiguous tile rows across ranks
 into a ROW BAND of the frame (its tiles' rows plus the tile overlap) and the bands are added into rank 0's frame
 by point-to-point transfers in rank order (BandCanvas; SURVEY.md §8e: a reduce of row-band buffers to rank 0, RCCL
 having no gather), so no rank but 0 holds a full-frame canvas (BASELINE.json config 4).
+
+Stain normalisation at inference (stain.py; the reference normalises tiles when it builds its datasets): a predictor
+with `stain_normalizer` set accepts raw uint8 RGB tiles / images, normalises every tile on the device and goes on with
+the fused gray plane. Without one nothing changes.
 """
 from __future__ import annotations
 
@@ -41,13 +45,18 @@ def _to_dev(image, device):
     return image
 
 
+def _is_u8(t):
+    return t.dtype == (np.uint8 if isinstance(t, np.ndarray) else torch.uint8)
+
+
 class HipUnetPredictor:
     """GPU predictor: predict_single(image, mean, std) -> (S,S) float32 probabilities (main_out)."""
 
-    def __init__(self, net, max_batch=8):
+    def __init__(self, net, max_batch=8, stain_normalizer=None):
         self.net = net
         self.device = net.device
         self.max_batch = max_batch
+        self.stain_normalizer = stain_normalizer   # stain.ReinhardStainNormalizer: uint8 RGB tiles are accepted
         self._packed_step = None
 
     @property
@@ -61,14 +70,17 @@ class HipUnetPredictor:
 
     def predict_views(self, images, mean, std, views):
         """images: list/tensor of (S,S) tiles (device or host, may be strided windows); returns
-        (len(images), S, S) device tensor of TTA-merged probabilities."""
+        (len(images), S, S) device tensor of TTA-merged probabilities. With a stain normaliser the tiles may be raw
+        (S, S, 3) uint8 RGB."""
         n_img = len(images)
         nv = len(views)
-        S = images[0].shape[-1]
+        S = images[0].shape[-1] if self.stain_normalizer is None else images[0].shape[1]   # (S, S) or (S, S, 3)
         out = torch.empty((n_img, S, S), dtype=torch.float32, device=self.device)
         per = max(1, self.max_batch // nv)
         for i0 in range(0, n_img, per):
             chunk = images[i0:i0 + per]
+            if self.stain_normalizer is not None:
+                chunk = self._stain_normalize(chunk)
             B = len(chunk) * nv
             a = self.net.acts(B)
             for t, img in enumerate(chunk):
@@ -83,6 +95,18 @@ class HipUnetPredictor:
                     ops.tta_merge(p[t * nv:(t + 1) * nv], views, out[i0 + t])
         return out
 
+    def _stain_normalize(self, tiles):
+        """uint8 RGB tiles (S, S, 3), host or device, possibly windows of a larger image -> one normalised batch on the
+        device, each tile with its own statistics: the fused gray plane (S, S) f32 for a 1-channel network, the RGB as
+        f32 for a 3-channel one. Tiles that are not uint8 RGB pass through untouched."""
+        if not all(_is_u8(t) and t.ndim == 3 and t.shape[-1] == 3 for t in tiles):
+            return tiles
+        batch = torch.stack([torch.from_numpy(np.ascontiguousarray(t)) if isinstance(t, np.ndarray) else t
+                             for t in tiles]).to(self.device)
+        if getattr(self.net, "in_ch", 1) == 3:
+            return self.stain_normalizer.normalize_tiles(batch).float()
+        return self.stain_normalizer.normalize_tiles(batch, out_gray=True)
+
     def predict_single(self, image, mean, std):
         """segmentation_inference.py:153-158 — returns a new float32 numpy array."""
         return self.predict_views([image], mean, std, [0])[0].cpu().numpy()
@@ -92,8 +116,9 @@ class AdiposeUNet:
     """Inference wrapper with the reference's method surface (build_model / load_weights /
     predict_single / predict). ``dtype='f32'`` reproduces the reference's fp32 numerics."""
 
-    def __init__(self, tile_size=1024, dtype="f32", device="cuda", max_batch=8):
+    def __init__(self, tile_size=1024, dtype="f32", device="cuda", max_batch=8, stain_normalizer=None):
         self.net = None
+        self.stain_normalizer = stain_normalizer
         self.use_deep_supervision = False
         self.tile_size = tile_size
         self.dtype = dtype
@@ -108,7 +133,7 @@ class AdiposeUNet:
         cpad = INFER_CPAD if self.dtype == "bf16" else None
         self.net = AdiposeV3Net(1, self.tile_size, dtype=self.dtype, device=self.device, init_nb=init_nb, cpad=cpad,
                                 dropout_rate=dropout_rate, deep_supervision=use_deep_supervision)
-        self._pred = HipUnetPredictor(self.net, self.max_batch)
+        self._pred = HipUnetPredictor(self.net, self.max_batch, self.stain_normalizer)
         return self.net
 
     def load_weights(self, weights_path: str):
@@ -117,9 +142,11 @@ class AdiposeUNet:
         print(f"✓ Loaded weights from {weights_path}")
 
     def predict_single(self, image, mean, std):
+        self._pred.stain_normalizer = self.stain_normalizer
         return self._pred.predict_single(image, mean, std)
 
     def predict_views(self, images, mean, std, views):
+        self._pred.stain_normalizer = self.stain_normalizer
         return self._pred.predict_views(images, mean, std, views)
 
     def predict(self, image, mean, std, use_tta=False, tta_mode="basic"):
@@ -354,8 +381,12 @@ class SlidingWindowInference:
         if not hasattr(model, "predict_views"):
             raise TypeError("GPU sliding window needs a HIP predictor (AdiposeUNet / HipUnetPredictor)")
         dev = model.net.device if hasattr(model, "net") else torch.device("cuda")
-        img = _to_dev(image, dev)
-        h, w = img.shape
+        if getattr(model, "stain_normalizer", None) is not None and _is_u8(image):
+            # raw RGB (H, W, 3): uploaded as bytes, every window is stain-normalised by predict_views
+            img = (torch.from_numpy(np.ascontiguousarray(image)) if isinstance(image, np.ndarray) else image).to(dev)
+        else:
+            img = _to_dev(image, dev)
+        h, w = img.shape[:2]
         T = self.tile_size
         positions = self.extract_tile_positions((h, w))
         mine = self.shard(positions)

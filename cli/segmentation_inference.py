@@ -8,7 +8,9 @@ weights (defaults 0/1 with a warning, :232-249), images of the wrong size are sk
 (:441-444), `masks/{stem}_mask.tif` (uint8 0/1), optional `probabilities/{stem}_prob.tif` (uint8
 prob*255) and `overlays/{stem}_overlay.png`; returns 0/1. All TTA views of a tile run as one batched
 forward on the GPU. Extra flags of this build: --tile (the reference hard-codes 1024), --dtype
-(f32 = the reference's numerics, bf16 = throughput), --batch (tiles x views per forward).
+(f32 = the reference's numerics, bf16 = throughput), --batch (tiles x views per forward), and
+--stain-reference IMAGE | --stain-metadata JSON: the tiles are raw RGB and are Reinhard stain-normalised on the GPU
+(src/utils/stain_normalization.py, which the reference applies when it builds its datasets) before the network.
 """
 import argparse
 import json
@@ -66,6 +68,12 @@ def build_parser():
     p.add_argument("--tile", type=int, default=1024, help="tile size the network is built for (reference: 1024)")
     p.add_argument("--dtype", type=str, default="f32", choices=["f32", "bf16"])
     p.add_argument("--batch", type=int, default=8, help="tiles x TTA views per batched forward")
+    # Reinhard stain normalisation of raw RGB tiles on the GPU (the reference normalises when it builds its datasets)
+    g = p.add_mutually_exclusive_group()
+    g.add_argument("--stain-reference", type=str, default=None, metavar="PATH",
+                   help="reference RGB image: tiles are read as RGB and stain-normalised towards it")
+    g.add_argument("--stain-metadata", type=str, default=None, metavar="PATH",
+                   help="the reference selector's JSON (selected_reference.path names the reference image)")
     return p
 
 
@@ -92,7 +100,7 @@ def main(argv=None):
 
     import _adipose_pkg  # noqa: F401
     from adipose_amd.checkpoint import resolve_weights_file
-    from adipose_amd.data import read_gray, write_mask
+    from adipose_amd.data import read_gray, read_rgb, write_mask
     from adipose_amd.predictor import AdiposeUNet, TestTimeAugmentation
 
     print("Loading model...")
@@ -104,7 +112,16 @@ def main(argv=None):
     if weights_file.lower().endswith(".onnx"):
         print("❌ ONNX weights are not supported by the HIP engine (export the Keras-named weights instead)")
         return 1
-    model = AdiposeUNet(tile_size=args.tile, dtype=args.dtype, max_batch=args.batch)
+    normalizer = None
+    if args.stain_reference or args.stain_metadata:
+        from adipose_amd.stain import ReinhardStainNormalizer, load_best_reference
+        try:   # (both print the reference's name and LAB statistics)
+            normalizer = (ReinhardStainNormalizer(args.stain_reference) if args.stain_reference
+                          else load_best_reference(args.stain_metadata))
+        except (FileNotFoundError, ValueError) as e:
+            print(f"❌ {e}")
+            return 1
+    model = AdiposeUNet(tile_size=args.tile, dtype=args.dtype, max_batch=args.batch, stain_normalizer=normalizer)
     model.build_model()
     model.load_weights(weights_file)
     mean, std = load_normalization_stats(checkpoint_dir)
@@ -122,14 +139,15 @@ def main(argv=None):
     t0 = time.time()
     for img_path in image_files:
         try:
-            image = read_gray(img_path)
+            image = read_gray(img_path) if normalizer is None else read_rgb(img_path)
         except Exception:  # cv2.imread returns None on unreadable files (:437-439)
             print(f"⚠️  Warning: Failed to load {img_path.name}, skipping")
             continue
-        if image.shape != (args.tile, args.tile):
+        if image.shape[:2] != (args.tile, args.tile):
             print(f"⚠️  Warning: {img_path.name} is {image.shape}, expected ({args.tile}, {args.tile}), skipping")
             continue
-        image = image.astype(np.float32)
+        if normalizer is None:
+            image = image.astype(np.float32)
         pred = tta.predict_with_tta(model, image, mean, std) if tta is not None else model.predict_single(image, mean, std)
         if args.save_probability:
             write_mask(prob_dir / f"{img_path.stem}_prob.tif", (pred * 255).astype(np.uint8))

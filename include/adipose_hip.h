@@ -412,6 +412,20 @@ int adp_aug_remap(int H, int W, const float* src, const float* msrc, const doubl
 int adp_percentile_normalize(size_t n, const float* src, float* dst, double p_low, double p_high, void* work,
                              float* p_out, adp_stream_t s);
 
+/* ---- Reinhard stain normalisation of packed uint8 RGB tiles (N, H, W, 3), each tile with its own statistics
+ *      (src/utils/stain_normalization.py:32-146; build_dataset.py:1234-1238 applies it tile by tile). rgb2lab /
+ *      lab2rgb are skimage's documented D65 / 2-degree conversions; per-pixel maths f32, sums f64 ------------- */
+/* per-tile LAB statistics: stats[n] = {meanL, meanA, meanB, stdL, stdA, stdB} f64, population std
+ * (ReinhardStainNormalizer._calculate_lab_stats, :76-92). Deterministic (fixed-order partials, no float atomics);
+ * sums are of deviations from the tile's first pixel, so a constant tile has std exactly 0 */
+int adp_stain_lab_stats(int N, int H, int W, const uint8_t* rgb, double* stats, adp_stream_t s);
+/* normalize_image (:94-146): (lab - src_mean) * (tgt_std / src_std) + tgt_mean per channel (tgt_mean where
+ * src_std == 0), lab2rgb, clip to [0, 1], uint8 by truncation of x * 255. src_stats (N, 6) device f64 as written by
+ * adp_stain_lab_stats; tgt[6] HOST f64 in the same order. rgb_out (N, H, W, 3) u8 and / or gray_out (N, H, W) f32 =
+ * (R*19595 + G*38470 + B*7471 + 0x8000) >> 16 of the output bytes (PIL mode L); either may be NULL, not both */
+int adp_stain_reinhard_apply(int N, int H, int W, const uint8_t* rgb, const double* src_stats, const double* tgt,
+                             uint8_t* rgb_out, float* gray_out, adp_stream_t s);
+
 /* ---- optimizer (Keras Adam / AdamW, :800-806) --------------------------------------------- */
 int adp_adam(size_t n, float* param, const float* grad, float* m, float* v, float lr, float beta1,
              float beta2, float eps, int step, float weight_decay, float grad_scale, adp_stream_t s);
