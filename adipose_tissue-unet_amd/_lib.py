@@ -118,6 +118,7 @@ _SIGS = {
     "adp_percentile_normalize": [_S, _P, _P, C.c_double, C.c_double, _P, _P, _P],
     "adp_stain_lab_stats": [_I, _I, _I, _P, _P, _P],
     "adp_stain_reinhard_apply": [_I, _I, _I, _P, _P, C.POINTER(C.c_double), _P, _P, _P],
+    "adp_tile_qc": [_I, _I, _I, _P, C.c_longlong, _P, _I, _P, _P],
     "adp_create": [_P, _I, _P],
     "adp_destroy": [_P],
     "adp_param_size": [_P, C.c_char_p, _I, C.POINTER(C.c_size_t)],

@@ -39,6 +39,7 @@ enum class Slot {
   BoundaryDist,  // adp_boundary_metrics: the four distance fields
   BoundarySort,  // adp_boundary_metrics: surface distances and the sort's temporary
   StainPart,     // adp_stain_lab_stats: one row of six f64 sums per block
+  TileQcPart,    // adp_tile_qc: one row of three int64 sums per block
   Count
 };
 void* scratch(Slot slot, size_t bytes, hipStream_t s);

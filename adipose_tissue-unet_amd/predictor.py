@@ -20,6 +20,11 @@ having no gather), so no rank but 0 holds a full-frame canvas (BASELINE.json con
 Stain normalisation at inference (stain.py; the reference normalises tiles when it builds its datasets): a predictor
 with `stain_normalizer` set accepts raw uint8 RGB tiles / images, normalises every tile on the device and goes on with
 the fused gray plane. Without one nothing changes.
+
+Tile quality control at inference (quality.py; the reference's classify_tiles_batch lets only `tissue` tiles reach a
+network): a predictor with `tile_filter` set (a quality.TileQC) classifies raw uint8 RGB tiles / windows on the device
+and skips the forward for those in `skip_classes` (default: `empty`), whose probability map is all zero. Opt-in: with
+tile_filter=None every path runs as before.
 """
 from __future__ import annotations
 
@@ -49,14 +54,31 @@ def _is_u8(t):
     return t.dtype == (np.uint8 if isinstance(t, np.ndarray) else torch.uint8)
 
 
+def _is_rgb_u8(t):
+    return _is_u8(t) and t.ndim == 3 and t.shape[-1] == 3
+
+
+def _pil_gray(rgb):
+    """PIL's mode-L gray of a uint8 RGB tile as f32 (stain.gray_from_rgb_np, = data.read_gray of the same file), on
+    the host for an array and on its device for a tensor."""
+    if isinstance(rgb, np.ndarray):
+        from .stain import gray_from_rgb_np
+        return gray_from_rgb_np(rgb)
+    v = rgb.to(torch.int32)
+    return ((v[..., 0] * 19595 + v[..., 1] * 38470 + v[..., 2] * 7471 + 0x8000) >> 16).to(torch.float32)
+
+
 class HipUnetPredictor:
     """GPU predictor: predict_single(image, mean, std) -> (S,S) float32 probabilities (main_out)."""
 
-    def __init__(self, net, max_batch=8, stain_normalizer=None):
+    def __init__(self, net, max_batch=8, stain_normalizer=None, tile_filter=None, skip_classes=("empty",)):
         self.net = net
         self.device = net.device
         self.max_batch = max_batch
         self.stain_normalizer = stain_normalizer   # stain.ReinhardStainNormalizer: uint8 RGB tiles are accepted
+        self.tile_filter = tile_filter             # quality.TileQC: uint8 RGB tiles are classified, some skipped
+        self.skip_classes = tuple(skip_classes)
+        self.last_tile_classes = None              # classes of the last predict_views call's tiles, in input order
         self._packed_step = None
 
     @property
@@ -68,19 +90,36 @@ class HipUnetPredictor:
         outs = net.forward(batch, train=False, pack=True)
         return outs["main_out"]
 
-    def predict_views(self, images, mean, std, views):
+    def predict_views(self, images, mean, std, views, classify=True):
         """images: list/tensor of (S,S) tiles (device or host, may be strided windows); returns
-        (len(images), S, S) device tensor of TTA-merged probabilities. With a stain normaliser the tiles may be raw
-        (S, S, 3) uint8 RGB."""
+        (len(images), S, S) device tensor of TTA-merged probabilities. With a stain normaliser or a tile filter the
+        tiles may be raw (S, S, 3) uint8 RGB. With a tile filter (and classify=True; the sliding window, which has
+        classified its windows already, passes False) uint8 RGB tiles are classified in one call: those in
+        skip_classes get an all-zero map and take no part in any forward; last_tile_classes holds the classes."""
         n_img = len(images)
         nv = len(views)
-        S = images[0].shape[-1] if self.stain_normalizer is None else images[0].shape[1]   # (S, S) or (S, S, 3)
+        plain = self.stain_normalizer is None and self.tile_filter is None
+        S = images[0].shape[-1] if plain else images[0].shape[1]   # (S, S) or (S, S, 3)
         out = torch.empty((n_img, S, S), dtype=torch.float32, device=self.device)
         per = max(1, self.max_batch // nv)
-        for i0 in range(0, n_img, per):
-            chunk = images[i0:i0 + per]
+        todo = list(range(n_img))
+        self.last_tile_classes = None
+        if self.tile_filter is not None and classify and all(_is_rgb_u8(t) for t in images):
+            self.last_tile_classes = self.tile_filter.classify(list(images))
+            todo = [i for i in todo if self.last_tile_classes[i] not in self.skip_classes]
+            if len(todo) < n_img:
+                out.zero_()
+        for j0 in range(0, len(todo), per):
+            sel = todo[j0:j0 + per]
+            i0 = sel[0]
+            chunk = images[i0:i0 + len(sel)] if sel[-1] - i0 + 1 == len(sel) else [images[i] for i in sel]
             if self.stain_normalizer is not None:
                 chunk = self._stain_normalize(chunk)
+            elif self.tile_filter is not None and all(_is_rgb_u8(t) for t in chunk):
+                # raw RGB without a normaliser: PIL's gray for a 1-channel network, the RGB as float for a 3-channel one
+                rgb3 = getattr(self.net, "in_ch", 1) == 3
+                chunk = [(torch.from_numpy(np.ascontiguousarray(t)) if isinstance(t, np.ndarray) else t)
+                         .to(self.device).float() if rgb3 else _pil_gray(t) for t in chunk]
             B = len(chunk) * nv
             a = self.net.acts(B)
             for t, img in enumerate(chunk):
@@ -90,9 +129,9 @@ class HipUnetPredictor:
             p = self._forward(B)
             for t in range(len(chunk)):
                 if nv == 1:
-                    ops.cast(p[t], out[i0 + t])
+                    ops.cast(p[t], out[sel[t]])
                 else:
-                    ops.tta_merge(p[t * nv:(t + 1) * nv], views, out[i0 + t])
+                    ops.tta_merge(p[t * nv:(t + 1) * nv], views, out[sel[t]])
         return out
 
     def _stain_normalize(self, tiles):
@@ -116,9 +155,12 @@ class AdiposeUNet:
     """Inference wrapper with the reference's method surface (build_model / load_weights /
     predict_single / predict). ``dtype='f32'`` reproduces the reference's fp32 numerics."""
 
-    def __init__(self, tile_size=1024, dtype="f32", device="cuda", max_batch=8, stain_normalizer=None):
+    def __init__(self, tile_size=1024, dtype="f32", device="cuda", max_batch=8, stain_normalizer=None,
+                 tile_filter=None, skip_classes=("empty",)):
         self.net = None
         self.stain_normalizer = stain_normalizer
+        self.tile_filter = tile_filter
+        self.skip_classes = tuple(skip_classes)
         self.use_deep_supervision = False
         self.tile_size = tile_size
         self.dtype = dtype
@@ -133,7 +175,8 @@ class AdiposeUNet:
         cpad = INFER_CPAD if self.dtype == "bf16" else None
         self.net = AdiposeV3Net(1, self.tile_size, dtype=self.dtype, device=self.device, init_nb=init_nb, cpad=cpad,
                                 dropout_rate=dropout_rate, deep_supervision=use_deep_supervision)
-        self._pred = HipUnetPredictor(self.net, self.max_batch, self.stain_normalizer)
+        self._pred = HipUnetPredictor(self.net, self.max_batch, self.stain_normalizer, self.tile_filter,
+                                      self.skip_classes)
         return self.net
 
     def load_weights(self, weights_path: str):
@@ -141,13 +184,20 @@ class AdiposeUNet:
         load_weights(self.net, weights_path, by_name=True, skip_mismatch=False)
         print(f"✓ Loaded weights from {weights_path}")
 
-    def predict_single(self, image, mean, std):
-        self._pred.stain_normalizer = self.stain_normalizer
-        return self._pred.predict_single(image, mean, std)
+    def _sync(self):
+        p = self._pred
+        p.stain_normalizer, p.tile_filter, p.skip_classes = self.stain_normalizer, self.tile_filter, tuple(self.skip_classes)
+        return p
 
-    def predict_views(self, images, mean, std, views):
-        self._pred.stain_normalizer = self.stain_normalizer
-        return self._pred.predict_views(images, mean, std, views)
+    @property
+    def last_tile_classes(self):
+        return self._pred.last_tile_classes if self._pred is not None else None
+
+    def predict_single(self, image, mean, std):
+        return self._sync().predict_single(image, mean, std)
+
+    def predict_views(self, images, mean, std, views, classify=True):
+        return self._sync().predict_views(images, mean, std, views, classify)
 
     def predict(self, image, mean, std, use_tta=False, tta_mode="basic"):
         """full_evaluation_enhanced.py:1323-1353 -> (pred, timing_info)"""
@@ -339,6 +389,7 @@ class SlidingWindowInference:
         self.blend_mode = blend_mode
         self.blender = GaussianBlender(tile_size) if blend_mode == "gaussian" else LinearBlender()
         self.group = process_group
+        self.last_tile_classes = None   # classes of this rank's windows in the last call (a model with a tile filter)
         if verbose:
             print(f"[SlidingWindow] Initialized: tile={tile_size}, stride={self.stride}, "
                   f"overlap={overlap:.1%}, blend={blend_mode}")
@@ -381,8 +432,9 @@ class SlidingWindowInference:
         if not hasattr(model, "predict_views"):
             raise TypeError("GPU sliding window needs a HIP predictor (AdiposeUNet / HipUnetPredictor)")
         dev = model.net.device if hasattr(model, "net") else torch.device("cuda")
-        if getattr(model, "stain_normalizer", None) is not None and _is_u8(image):
-            # raw RGB (H, W, 3): uploaded as bytes, every window is stain-normalised by predict_views
+        tile_filter = getattr(model, "tile_filter", None)
+        if (getattr(model, "stain_normalizer", None) is not None or tile_filter is not None) and _is_u8(image):
+            # raw RGB (H, W, 3): uploaded as bytes, every window is stain-normalised / converted by predict_views
             img = (torch.from_numpy(np.ascontiguousarray(image)) if isinstance(image, np.ndarray) else image).to(dev)
         else:
             img = _to_dev(image, dev)
@@ -401,12 +453,32 @@ class SlidingWindowInference:
             canvas = BandCanvas((h, w), bands[dist.get_rank(self.group)], dev)
         wmap = self.blender.device_weights(dev, T, T)
         per = max(1, getattr(model, "max_batch", 8) // len(views))
-        for i0 in range(0, len(mine), per):
-            chunk = mine[i0:i0 + per]
-            tiles = [img[y:y + T, x:x + T] for y, x in chunk]
-            probs = model.predict_views(tiles, mean, std, views)
-            for (y, x), p in zip(chunk, probs):
-                canvas.add(p, wmap, y, x)
+        # tile quality control: this rank's windows are classified in place with one launch; a skipped window enters
+        # the canvas as a zero tile with its blending weight (the network is taken to have said "background")
+        self.last_tile_classes = None
+        skip, kw, zero = [False] * len(mine), {}, None
+        if tile_filter is not None and _is_rgb_u8(img) and mine:
+            self.last_tile_classes = tile_filter.classify_windows(img, mine, T)
+            skip = [c in tuple(getattr(model, "skip_classes", ("empty",))) for c in self.last_tile_classes]
+            kw = {"classify": False}
+            if any(skip):
+                zero = torch.zeros((T, T), dtype=torch.float32, device=dev)
+        pending = []   # windows in order; forwarded (and all of them blended, in order) once `per` are to be predicted
+
+        def flush():
+            live = [pos for pos, s in pending if not s]
+            probs = iter(model.predict_views([img[y:y + T, x:x + T] for y, x in live], mean, std, views, **kw)
+                         if live else ())
+            for (y, x), s in pending:
+                canvas.add(zero if s else next(probs), wmap, y, x)
+            pending.clear()
+
+        for pos, s in zip(mine, skip):
+            pending.append((pos, s))
+            if sum(1 for _, sk in pending if not sk) == per:
+                flush()
+        if pending:
+            flush()
         if self.group is not None and not canvas.reduce_to_root(self.group, bands):
             if not broadcast:
                 return None   # (the blended frame lives on rank 0 only)

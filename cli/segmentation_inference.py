@@ -11,6 +11,11 @@ forward on the GPU. Extra flags of this build: --tile (the reference hard-codes 
 (f32 = the reference's numerics, bf16 = throughput), --batch (tiles x views per forward), and
 --stain-reference IMAGE | --stain-metadata JSON: the tiles are raw RGB and are Reinhard stain-normalised on the GPU
 (src/utils/stain_normalization.py, which the reference applies when it builds its datasets) before the network.
+--tile-qc: the tiles are raw RGB and are sorted into empty / blurry / tissue on the GPU first (the reference's
+classify_tiles_batch, build_dataset.py:1253-1284; --white-threshold, --white-ratio-limit, --blurry-threshold are its
+defaults). Empty tiles (with --skip-blurry also blurry ones) get an all-zero mask without a forward; `tile_qc.csv` in
+the output directory lists every tile's measurements and class. The files of the other tiles are what they are without
+the flag.
 """
 import argparse
 import json
@@ -74,6 +79,15 @@ def build_parser():
                    help="reference RGB image: tiles are read as RGB and stain-normalised towards it")
     g.add_argument("--stain-metadata", type=str, default=None, metavar="PATH",
                    help="the reference selector's JSON (selected_reference.path names the reference image)")
+    # tile quality control on the GPU (the reference sorts tiles when it builds its datasets; only tissue is trained on)
+    q = p.add_argument_group("tile quality control")
+    q.add_argument("--tile-qc", action="store_true", default=False,
+                   help="tiles are read as RGB and classified empty / blurry / tissue; skipped tiles get a zero mask")
+    q.add_argument("--white-threshold", type=int, default=235, help="a pixel is white when R, G and B reach this")
+    q.add_argument("--white-ratio-limit", type=float, default=0.70, help="empty: more than this share of white pixels")
+    q.add_argument("--blurry-threshold", type=float, default=7.5, help="blurry: variance of the Laplacian below this")
+    q.add_argument("--skip-blurry", action="store_true", default=False,
+                   help="skip blurry tiles too (default: only empty ones, as the reference keeps blurry tiles)")
     return p
 
 
@@ -130,6 +144,11 @@ def main(argv=None):
         tta = TestTimeAugmentation(mode=args.tta_mode)
         print(f"✓ TTA enabled: {args.tta_mode} mode ({len(tta.transforms)} augmentations)")
     color = COLORS[args.overlay_color]
+    qc, qc_rows, skip_classes = None, [], ("empty", "blurry") if args.skip_blurry else ("empty",)
+    if args.tile_qc:
+        from adipose_amd.quality import CLASSES, TileQC, measures
+        qc = TileQC(args.white_threshold, args.white_ratio_limit, args.blurry_threshold)
+    raw_rgb = normalizer is not None or qc is not None
 
     image_files = [f for f in images_dir.iterdir() if f.suffix.lower() in IMAGE_EXTS and f.is_file()]
     if not image_files:
@@ -139,16 +158,33 @@ def main(argv=None):
     t0 = time.time()
     for img_path in image_files:
         try:
-            image = read_gray(img_path) if normalizer is None else read_rgb(img_path)
+            image = read_rgb(img_path) if raw_rgb else read_gray(img_path)
         except Exception:  # cv2.imread returns None on unreadable files (:437-439)
             print(f"⚠️  Warning: Failed to load {img_path.name}, skipping")
             continue
         if image.shape[:2] != (args.tile, args.tile):
             print(f"⚠️  Warning: {img_path.name} is {image.shape}, expected ({args.tile}, {args.tile}), skipping")
             continue
+        skipped = False
+        if qc is not None:
+            if image.ndim != 3 or image.shape[2] != 3:
+                print(f"⚠️  Warning: {img_path.name} is not RGB, skipping")
+                continue
+            sums = qc.sums(image)
+            ratio, var = measures(sums)
+            cls = qc.classes_from_sums(sums)[0]
+            skipped = cls in skip_classes
+            qc_rows.append((img_path.name, f"{ratio[0]:.6f}", f"{var[0]:.6f}", cls, int(skipped)))
+            if normalizer is None:   # the gray plane read_gray gives for the same file
+                from adipose_amd.stain import gray_from_rgb_np
+                image = gray_from_rgb_np(image)
         if normalizer is None:
             image = image.astype(np.float32)
-        pred = tta.predict_with_tta(model, image, mean, std) if tta is not None else model.predict_single(image, mean, std)
+        if skipped:   # no forward: the network is taken to have said "background"
+            pred = np.zeros((args.tile, args.tile), np.float32)
+        else:
+            pred = (tta.predict_with_tta(model, image, mean, std) if tta is not None
+                    else model.predict_single(image, mean, std))
         if args.save_probability:
             write_mask(prob_dir / f"{img_path.stem}_prob.tif", (pred * 255).astype(np.uint8))
         binary = (pred > args.threshold).astype(np.uint8)
@@ -158,9 +194,19 @@ def main(argv=None):
             Image.fromarray(create_overlay_visualization(image, binary, color)).save(
                 overlays_dir / f"{img_path.stem}_overlay.png")
     elapsed = time.time() - t0
+    if qc is not None:
+        import csv
+        with open(output_dir / "tile_qc.csv", "w", newline="") as f:
+            w = csv.writer(f)
+            w.writerow(["name", "white_ratio", "lap_var", "class", "skipped"])
+            w.writerows(qc_rows)
     print(f"\n{'=' * 80}\nINFERENCE COMPLETE\n{'=' * 80}")
     print(f"Processed: {len(image_files)} images")
     print(f"Time: {elapsed:.1f}s ({elapsed / len(image_files):.2f}s per image)")
+    if qc is not None:
+        counts = ", ".join(f"{c}={sum(1 for r in qc_rows if r[3] == c)}" for c in CLASSES)
+        print(f"Tile QC: {counts}; skipped {sum(r[4] for r in qc_rows)} (classes {', '.join(skip_classes)}); "
+              f"{output_dir / 'tile_qc.csv'}")
     print(f"\nOutput saved to:\n  Masks: {masks_dir}")
     if args.save_overlays:
         print(f"  Overlays: {overlays_dir}")

@@ -426,6 +426,19 @@ int adp_stain_lab_stats(int N, int H, int W, const uint8_t* rgb, double* stats, 
 int adp_stain_reinhard_apply(int N, int H, int W, const uint8_t* rgb, const double* src_stats, const double* tgt,
                              uint8_t* rgb_out, float* gray_out, adp_stream_t s);
 
+/* ---- tile quality control (classify_tiles_batch, Segmentation/build_dataset.py:1253-1284): integer sums behind
+ *      white_ratio and the variance of the Laplacian; exact, so independent of N, the grid and the run ---------- */
+/* Per-tile quality sums of packed uint8 RGB tiles. Byte c of pixel (y, x) of tile n is
+ * rgb[origin(n) + y*row_pitch + 3*x + c]; origin(n) = origins[n] (device array of N byte offsets, so the
+ * tiles may be overlapping windows of one image), or n*H*row_pitch when origins is NULL. row_pitch >= 3*W
+ * (0 means 3*W). sums: (N, 4) int64 on the device: {white, S1, S2, H*W}.
+ * white: pixels with R, G and B all >= white_threshold; gray = (R*9798 + G*19235 + B*3735 + 16384) >> 15 (OpenCV's
+ * 8-bit BGR2GRAY); lap = g(y-1,x) + g(y+1,x) + g(y,x-1) + g(y,x+1) - 4 g(y,x) with reflect-101 borders within the
+ * tile (cv2.Laplacian, ksize 1); S1 = sum lap, S2 = sum lap^2. Fails (message, nothing launched, sums untouched) on a
+ * NULL rgb or sums, N < 1, H < 2 or W < 2, or a non-zero row_pitch below 3*W */
+int adp_tile_qc(int N, int H, int W, const uint8_t* rgb, long long row_pitch, const long long* origins,
+                int white_threshold, long long* sums, adp_stream_t s);
+
 /* ---- optimizer (Keras Adam / AdamW, :800-806) --------------------------------------------- */
 int adp_adam(size_t n, float* param, const float* grad, float* m, float* v, float lr, float beta1,
              float beta2, float eps, int step, float weight_decay, float grad_scale, adp_stream_t s);
