@@ -119,6 +119,11 @@ _SIGS = {
     "adp_stain_lab_stats": [_I, _I, _I, _P, _P, _P],
     "adp_stain_reinhard_apply": [_I, _I, _I, _P, _P, C.POINTER(C.c_double), _P, _P, _P],
     "adp_tile_qc": [_I, _I, _I, _P, C.c_longlong, _P, _I, _P, _P],
+    "adp_cc_label": [_I, _I, _I, _P, _I, _F, _I, _P, _P],
+    "adp_cc_areas": [_I, _I, _I, _P, _P, _P],
+    "adp_cc_filter": [_I, _I, _I, _P, _P, _I, _P, _P, _P],
+    "adp_cc_table": [_I, _I, _I, _P, _I, _P, _P, _P],
+    "adp_cc_relabel": [_I, _I, _I, _P, _P, _P],
     "adp_create": [_P, _I, _P],
     "adp_destroy": [_P],
     "adp_param_size": [_P, C.c_char_p, _I, C.POINTER(C.c_size_t)],

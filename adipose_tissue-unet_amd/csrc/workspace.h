@@ -40,6 +40,7 @@ enum class Slot {
   BoundarySort,  // adp_boundary_metrics: surface distances and the sort's temporary
   StainPart,     // adp_stain_lab_stats: one row of six f64 sums per block
   TileQcPart,    // adp_tile_qc: one row of three int64 sums per block
+  CcScan,        // adp_cc_table / adp_cc_relabel: the ranks of the roots and the scan's temporary
   Count
 };
 void* scratch(Slot slot, size_t bytes, hipStream_t s);

@@ -506,8 +506,11 @@ def run_publication_evaluation(val_data_root: str, weights_path: str, output_dir
                                use_boundary_refine: bool = False, refine_kernel: int = 5,
                                adaptive_threshold: bool = False, save_overlays: bool = False, n_positive: int = 120,
                                n_negative: int = 30, *, tile_size: int = 1024, dtype: str = "f32",
-                               max_batch: int = 8) -> ComprehensiveMetrics:
-    """:1446-1958 (same steps, prints and output files). tile_size / dtype / max_batch: this build."""
+                               max_batch: int = 8, min_cc_px: int = 0) -> ComprehensiveMetrics:
+    """:1446-1958 (same steps, prints and output files). tile_size / dtype / max_batch: this build. min_cc_px > 0:
+    the pixel metrics are computed on the binarised prediction without its 8-connected components of fewer than
+    min_cc_px pixels (components.remove_small_components, the treatment the ground-truth masks were built with);
+    0 leaves every number as it is."""
     import pandas as pd
 
     from .predictor import AdiposeUNet, SlidingWindowInference
@@ -586,12 +589,22 @@ def run_publication_evaluation(val_data_root: str, weights_path: str, output_dir
         slides[extract_slide_id(p)].append(i)
     n_slides = len(slides)
     print(f"✓ Grouped {n_files} tiles into {n_slides} slides")
+    if min_cc_px > 0:
+        from .components import remove_small_components
+        print(f"✓ Components below {min_cc_px} px are removed before the pixel metrics")
+
+    def metric_pred(i):
+        if min_cc_px <= 0:
+            return preds[i]
+        binary = (preds[i] > optimal_threshold).astype(np.uint8)
+        return remove_small_components(binary, min_cc_px).astype(np.float32)   # 1 > threshold, 0 is not
+
     print(f"\nCalculating slide-level metrics with threshold {optimal_threshold:.2f}...")
     keys = ["dice_scores", "jaccard_indices", "sensitivities", "specificities", "precisions", "f1_scores",
             "accuracies", "roc_aucs", "pr_aucs", "hausdorff95s", "assds"]
     sm = {k: [] for k in keys}
     for sid, idxs in slides.items():
-        tm = [calculate_pixel_metrics(preds[i], trues[i], optimal_threshold) for i in idxs]
+        tm = [calculate_pixel_metrics(metric_pred(i), trues[i], optimal_threshold) for i in idxs]
         bm = [calculate_boundary_metrics(preds[i], trues[i], optimal_threshold) for i in idxs]
         am = [calculate_auc_metrics(preds[i], trues[i]) for i in idxs]
         for k, mk in (("dice_scores", "dice_score"), ("jaccard_indices", "jaccard_index"),
@@ -643,7 +656,7 @@ def run_publication_evaluation(val_data_root: str, weights_path: str, output_dir
             (od / b).mkdir(parents=True, exist_ok=True)
         dices = []
         for i, idx in enumerate(idxs):
-            dice = calculate_pixel_metrics(preds[idx], trues[idx], optimal_threshold)["dice_score"]
+            dice = calculate_pixel_metrics(metric_pred(idx), trues[idx], optimal_threshold)["dice_score"]
             dices.append(dice)
             b = categorize_by_dice(dice)
             counts[b] += 1
@@ -668,7 +681,7 @@ def run_publication_evaluation(val_data_root: str, weights_path: str, output_dir
         vd = output_dir / "visualizations"
         vd.mkdir(exist_ok=True)
         for i, idx in enumerate(np.linspace(0, n_files - 1, n_viz, dtype=int)):
-            dice = calculate_pixel_metrics(preds[idx], trues[idx], optimal_threshold)["dice_score"]
+            dice = calculate_pixel_metrics(metric_pred(idx), trues[idx], optimal_threshold)["dice_score"]
             create_4panel_visualization(images[idx], trues[idx], preds[idx], dice,
                                         str(vd / f"{dataset_name}_sample_{i + 1:02d}_{Path(paths[idx]).stem}.png"))
         print(f"✓ Saved visualizations to: {vd}")

@@ -305,7 +305,8 @@ def create_reconstruction_log(args, output_dir: Path, slide_results: List[Dict])
                           "stride": args.stride, "threshold": args.threshold, "blend_mode": args.blend_mode,
                           "use_tta": args.use_tta, "tta_mode": args.tta_mode if args.use_tta else None,
                           "boundary_refine": args.boundary_refine,
-                          "refine_kernel": args.refine_kernel if args.boundary_refine else None},
+                          "refine_kernel": args.refine_kernel if args.boundary_refine else None,
+                          **_component_settings(args)},
         "slides_processed": len(slide_results),
         "slide_results": slide_results,
         "summary_statistics": {
@@ -320,9 +321,26 @@ def create_reconstruction_log(args, output_dir: Path, slide_results: List[Dict])
     return path
 
 
+def _component_settings(args):
+    """The connected-component settings of a run, for the log: nothing when neither is set (the log of a run without
+    them is what it was)."""
+    min_cc, stats = int(getattr(args, "min_cc_px", 0) or 0), bool(getattr(args, "cell_stats", False))
+    if min_cc <= 0 and not stats:
+        return {}
+    return {"min_cc_px": min_cc, "cell_stats": stats,
+            "cell_min_area": int(getattr(args, "cell_min_area", 10)) if stats else None}
+
+
 def reconstruct_all_slides(args, model=None, process_group=None):
     """:586-866 — per slide: coverage check, dimensions, reconstruction, TIFF / PNG / metrics outputs.
-    ``model`` overrides building AdiposeUNet from args.weights (tests, custom predictors)."""
+    ``model`` overrides building AdiposeUNet from args.weights (tests, custom predictors).
+    args.min_cc_px > 0 (build_dataset.py's --min-cc-px): the slide prediction is thresholded on the device and its
+    8-connected components of fewer than min_cc_px pixels are removed (components.py); the 0 / 1 mask takes the
+    prediction's place in prediction_mask.tif, the overlays and the metrics. args.cell_stats: cell_stats.csv with one
+    row per slide, from the mask that is written."""
+    min_cc_px, cell_stats = int(getattr(args, "min_cc_px", 0) or 0), bool(getattr(args, "cell_stats", False))
+    post = min_cc_px > 0 or cell_stats
+    cell_rows = []
     print(f"\n{'=' * 80}\nFULL IMAGE RECONSTRUCTION FROM OVERLAPPING TILES\n{'=' * 80}")
     set_deterministic_seeds(1337)
     data_root = Path(args.data_root)
@@ -371,9 +389,21 @@ def reconstruct_all_slides(args, model=None, process_group=None):
             full_shape = get_full_image_dimensions(slide_id, positions, args.tile_size, args.stride, args.data_root)
         full_rgb, full_pred, full_gt = reconstruct_slide(
             model, tiles_info, full_shape, args.tile_size, args.stride, train_mean, train_std, blender, refiner,
-            args.use_tta, args.tta_mode, process_group=process_group)
+            args.use_tta, args.tta_mode, process_group=process_group, return_device=post)
         if not rank0:
             continue
+        if post:   # the 64 M-pixel planes are still on the device
+            from . import components as cc
+            if min_cc_px > 0:
+                lab = cc.label(full_pred, 8, threshold=float(args.threshold))
+                full_pred = cc.filter_small(lab, cc.areas(lab), min_cc_px, torch.float32)
+                del lab
+            if cell_stats:
+                st = cc.cell_statistics(full_pred, int(getattr(args, "cell_min_area", 10)), float(args.threshold))
+                cell_rows.append(cc.cell_stats_row(slide_id, st))
+                print(f"  Cells: {st['num_cells']} (coverage {st['tissue_coverage']:.1%})")
+            full_rgb, full_pred = full_rgb.cpu().numpy(), full_pred.cpu().numpy()
+            full_gt = None if full_gt is None else full_gt.cpu().numpy()
         slide_dir = output_dir / slide_id
         slide_dir.mkdir(parents=True, exist_ok=True)
         _save_tiff(slide_dir / "original_image.tif", (full_rgb * 255).astype(np.uint8))
@@ -414,6 +444,14 @@ def reconstruct_all_slides(args, model=None, process_group=None):
             mp = output_dir / "metrics" / f"{slide_id}_metrics.json"
             mp.parent.mkdir(parents=True, exist_ok=True)
             mp.write_text(json.dumps(res, indent=2, default=float))
+    if cell_stats and rank0:
+        import csv
+
+        from .components import CELL_STATS_HEADER
+        with open(output_dir / "cell_stats.csv", "w", newline="") as f:
+            w = csv.writer(f)
+            w.writerow(CELL_STATS_HEADER)
+            w.writerows(cell_rows)
     if results and rank0:
         rows = [{"slide_id": r["slide_id"], "dice_score": r["metrics"]["dice_score"],
                  "jaccard_iou": r["metrics"]["jaccard_index"], "sensitivity": r["metrics"]["sensitivity"],

@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def parse_args(argv=None):
+def build_parser():
     p = argparse.ArgumentParser(description="Reconstruct full images from overlapping tiles",
                                 formatter_class=argparse.RawDescriptionHelpFormatter)
     p.add_argument("--weights", type=str, required=True, help="Path to trained model weights")
@@ -35,7 +35,18 @@ def parse_args(argv=None):
     p.add_argument("--max-tiles", type=int, default=None)
     p.add_argument("--dtype", type=str, default="f32", choices=["f32", "bf16"])
     p.add_argument("--batch", type=int, default=8)
-    return p.parse_args(argv)
+    c = p.add_argument_group("connected components (on the device, on the whole-slide mask)")
+    c.add_argument("--min-cc-px", type=int, default=0,
+                   help="remove 8-connected components below this many pixels from the thresholded slide mask "
+                        "(build_dataset.py --min-cc-px; 0 = off); the mask, the overlays and the metrics then use it")
+    c.add_argument("--cell-stats", action="store_true", default=False,
+                   help="write cell_stats.csv: per slide num_cells, mean / median / min / max area, tissue_coverage")
+    c.add_argument("--cell-min-area", type=int, default=10, help="regions below this area are not counted as cells")
+    return p
+
+
+def parse_args(argv=None):
+    return build_parser().parse_args(argv)
 
 
 def main(argv=None):

@@ -88,6 +88,14 @@ def build_parser():
     q.add_argument("--blurry-threshold", type=float, default=7.5, help="blurry: variance of the Laplacian below this")
     q.add_argument("--skip-blurry", action="store_true", default=False,
                    help="skip blurry tiles too (default: only empty ones, as the reference keeps blurry tiles)")
+    c = p.add_argument_group("connected components (on the device)")
+    c.add_argument("--min-cc-px", type=int, default=0,
+                   help="remove 8-connected components below this many pixels from the binarised mask "
+                        "(build_dataset.py --min-cc-px; 0 = off)")
+    c.add_argument("--cell-stats", action="store_true", default=False,
+                   help="write cell_stats.csv: per image num_cells, mean / median / min / max area, tissue_coverage "
+                        "of the mask that is written")
+    c.add_argument("--cell-min-area", type=int, default=10, help="regions below this area are not counted as cells")
     return p
 
 
@@ -149,6 +157,12 @@ def main(argv=None):
         from adipose_amd.quality import CLASSES, TileQC, measures
         qc = TileQC(args.white_threshold, args.white_ratio_limit, args.blurry_threshold)
     raw_rgb = normalizer is not None or qc is not None
+    cell_rows = []
+    if args.min_cc_px > 0 or args.cell_stats:
+        import torch
+
+        from adipose_amd.components import (CELL_STATS_HEADER, cell_statistics, cell_stats_row,
+                                            remove_small_components)
 
     image_files = [f for f in images_dir.iterdir() if f.suffix.lower() in IMAGE_EXTS and f.is_file()]
     if not image_files:
@@ -188,6 +202,16 @@ def main(argv=None):
         if args.save_probability:
             write_mask(prob_dir / f"{img_path.stem}_prob.tif", (pred * 255).astype(np.uint8))
         binary = (pred > args.threshold).astype(np.uint8)
+        if skipped:   # all background: nothing to label
+            if args.cell_stats:
+                cell_rows.append(cell_stats_row(img_path.name))
+        elif args.min_cc_px > 0 or args.cell_stats:
+            mask_dev = torch.from_numpy(binary).cuda()
+            if args.min_cc_px > 0:
+                mask_dev = remove_small_components(mask_dev, args.min_cc_px)
+                binary = mask_dev.cpu().numpy()
+            if args.cell_stats:
+                cell_rows.append(cell_stats_row(img_path.name, cell_statistics(mask_dev, args.cell_min_area, 0.5)))
         write_mask(masks_dir / f"{img_path.stem}_mask.tif", binary)
         if args.save_overlays:
             from PIL import Image
@@ -200,6 +224,12 @@ def main(argv=None):
             w = csv.writer(f)
             w.writerow(["name", "white_ratio", "lap_var", "class", "skipped"])
             w.writerows(qc_rows)
+    if args.cell_stats:
+        import csv
+        with open(output_dir / "cell_stats.csv", "w", newline="") as f:
+            w = csv.writer(f)
+            w.writerow(CELL_STATS_HEADER)
+            w.writerows(cell_rows)
     print(f"\n{'=' * 80}\nINFERENCE COMPLETE\n{'=' * 80}")
     print(f"Processed: {len(image_files)} images")
     print(f"Time: {elapsed:.1f}s ({elapsed / len(image_files):.2f}s per image)")

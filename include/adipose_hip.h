@@ -439,6 +439,40 @@ int adp_stain_reinhard_apply(int N, int H, int W, const uint8_t* rgb, const doub
 int adp_tile_qc(int N, int H, int W, const uint8_t* rgb, long long row_pitch, const long long* origins,
                 int white_threshold, long long* sums, adp_stream_t s);
 
+/* ---- connected components of binary maps (remove_small_components, Segmentation/build_dataset.py:1122-1131 and
+ *      build_test_dataset.py:374, flag --min-cc-px: cv2.connectedComponentsWithStats(connectivity=8), keep
+ *      area >= min_px; analyze_cell_characteristics, pre-post-processing_tools/analysis/morphology
+ *      parameter_analysis/analyze_training_data.py:76-130: num_cells, areas, tissue_coverage). All stream-ordered,
+ *      none synchronises; integer results, exact and independent of N, the grid, the schedule and the run ---------- */
+#define ADP_CC_SRC_U8 0  /* foreground: byte != 0 */
+#define ADP_CC_SRC_F32 1 /* foreground: value > thr */
+/* region of the in-LDS labelling stage (tests place their shapes around it) */
+#define ADP_CC_REGION_ROWS 32
+#define ADP_CC_REGION_COLS 64
+/* labels (N, H, W) int32: 0 for background, else 1 + the raster index y*W + x, within the pixel's own image, of the
+ * first pixel (smallest index) of its component. src (N, H, W) of src_dtype; thr is used by ADP_CC_SRC_F32 only.
+ * connectivity 8 (cv2 connectivity=8, skimage measure.label's 2-D default) or 4 (scipy.ndimage.label's default).
+ * Fails (message, nothing launched) on a NULL pointer, N, H or W < 1, H*W > 2^31 - 2, a connectivity other than 4 / 8,
+ * or an unknown src_dtype */
+int adp_cc_label(int N, int H, int W, const void* src, int src_dtype, float thr, int connectivity, int* labels,
+                 adp_stream_t s);
+/* area (N, H, W) int32: the pixel count of a component at the position of its first pixel, 0 everywhere else.
+ * labels as written by adp_cc_label */
+int adp_cc_areas(int N, int H, int W, const int* labels, int* area, adp_stream_t s);
+/* remove_small_components: 1 where the pixel's component has area >= min_px, else 0; as uint8 and / or f32
+ * (either may be NULL, not both). area as written by adp_cc_areas */
+int adp_cc_filter(int N, int H, int W, const int* labels, const int* area, int min_px, uint8_t* out_u8, float* out_f32,
+                  adp_stream_t s);
+/* counts[n] = the number of components of image n (always the true number). table (N, max_rows, 8) int64, rows
+ * {first, area, x_min, y_min, x_max, y_max, sum_x, sum_y} in ascending order of `first` (row k: the component a raster
+ * scan meets k-th); components beyond max_rows are dropped, rows past counts[n] are zero. cv2's stats: width =
+ * x_max - x_min + 1, height = y_max - y_min + 1, centroid = (sum_x / area, sum_y / area). max_rows = 0 (table may
+ * then be NULL) only counts */
+int adp_cc_table(int N, int H, int W, const int* labels, int max_rows, long long* table, int* counts, adp_stream_t s);
+/* dense (N, H, W) int32: 0 for background, else 1 + the row of the pixel's component in adp_cc_table's order
+ * (labels 1..K in raster order of first pixel, as cv2 numbers them) */
+int adp_cc_relabel(int N, int H, int W, const int* labels, int* dense, adp_stream_t s);
+
 /* ---- optimizer (Keras Adam / AdamW, :800-806) --------------------------------------------- */
 int adp_adam(size_t n, float* param, const float* grad, float* m, float* v, float lr, float beta1,
              float beta2, float eps, int step, float weight_decay, float grad_scale, adp_stream_t s);
