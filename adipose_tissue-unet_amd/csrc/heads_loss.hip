@@ -166,7 +166,7 @@ __global__ __launch_bounds__(TPB) void head_bwd_kernel(size_t M, int Cs, int Cin
     float v[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[j] = (FAST || sc) ? fmaxf(fmaf(f[j], s_[j], h_[j]), 0.f) : f[j];
-    if constexpr (BNR) {   // the activation as adp_bn_apply materializes it (rounded to T)
+    if (BNR || sc) {   // the activation as adp_bn_apply materializes it and the forward read it (rounded to T)
       Grp<T> gv;
       grp_from_f(gv, v);
       grp_to_f(gv, v);
@@ -296,14 +296,20 @@ ADP_DEV float bil_w(int o, float scale, int n, int s) {
 
 __global__ void resize_bwd_kernel(int N, int Hs, int Ws, int Ho, int Wo, const float* dout, float* dsrc) {
   const float sy = (float)Hs / Ho, sx = (float)Ws / Wo;
-  const int fy = (Ho + Hs - 1) / Hs, fx = (Wo + Ws - 1) / Ws;
+  const float ry = (float)Ho / Hs, rx = (float)Wo / Ws;
   size_t total = (size_t)N * Hs * Ws;
   for (size_t i = blockIdx.x * (size_t)TPB + threadIdx.x; i < total; i += (size_t)gridDim.x * TPB) {
     int xs = (int)(i % Ws);
     size_t t = i / Ws;
     int ys = (int)(t % Hs), n = (int)(t / Hs);
-    int ya = max(0, (ys - 1) * fy - fy), yb = min(Ho - 1, (ys + 2) * fy + fy);
-    int xa = max(0, (xs - 1) * fx - fx), xb = min(Wo - 1, (xs + 2) * fx + fx);
+    // outputs whose source coordinate lies in (s - 1, s + 1): (s - 0.5) r - 0.5 < o < (s + 1.5) r - 0.5, one more
+    // either side for the f32 rounding of the bounds (bil_w decides the weights; the border rows and columns, which
+    // also take every clamped coordinate, are covered by the clamp to [0, n - 1]). A window in whole multiples of
+    // ceil(r) fell short of this range at non-integer ratios (Ho/Hs = 2.5: from the 10th row on).
+    int ya = max(0, (int)floorf(((float)ys - 0.5f) * ry - 0.5f) - 1);
+    int yb = min(Ho - 1, (int)ceilf(((float)ys + 1.5f) * ry - 0.5f) + 1);
+    int xa = max(0, (int)floorf(((float)xs - 0.5f) * rx - 0.5f) - 1);
+    int xb = min(Wo - 1, (int)ceilf(((float)xs + 1.5f) * rx - 0.5f) + 1);
     const float* d = dout + (size_t)n * Ho * Wo;
     float acc = 0.f;
     for (int yo = ya; yo <= yb; ++yo) {

@@ -316,6 +316,8 @@ int adp_head_softmax2_bwd(int dtype, size_t M, int C_stride, int Cin, const void
                           const float* bn_scale, const float* bn_shift, const float* p,
                           const float* dp, const void* addend, const void* mask, float mask_scale,
                           void* dx, float* dW, float* db, adp_stream_t s);
+/* bn_scale / bn_shift non-NULL (forward and backward alike): x is a pre-BN map and the head reads
+   dtype(relu(x*scale+shift)), the value adp_bn_apply would materialize; dW is taken from that rounded value */
 /* p = sigmoid(W x + b); W f32 [Cin], b f32 [1] */
 int adp_head_sigmoid_fwd(int dtype, size_t M, int C_stride, int Cin, const void* x, const float* W,
                          const float* b, const float* bn_scale, const float* bn_shift, float* p,
