@@ -124,6 +124,7 @@ _SIGS = {
     "adp_cc_filter": [_I, _I, _I, _P, _P, _I, _P, _P, _P],
     "adp_cc_table": [_I, _I, _I, _P, _I, _P, _P, _P],
     "adp_cc_relabel": [_I, _I, _I, _P, _P, _P],
+    "adp_cc_shape": [_I, _I, _I, _P, _I, _P, _P],
     "adp_create": [_P, _I, _P],
     "adp_destroy": [_P],
     "adp_param_size": [_P, C.c_char_p, _I, C.POINTER(C.c_size_t)],

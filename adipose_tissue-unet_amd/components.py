@@ -6,12 +6,16 @@ The reference treats a mask as a set of objects in two places:
       --min-cc-px): cv2.connectedComponentsWithStats(connectivity=8), keep the components with area >= min_px.
   analyze_cell_characteristics            pre-post-processing_tools/analysis/morphology parameter_analysis/
       analyze_training_data.py:76-130: skimage measure.label of mask > 0.5, then num_cells, the areas of the regions of
-      at least 10 px, and tissue_coverage.
+      at least 10 px, and tissue_coverage (cell_statistics); their perimeter, circularity, aspect ratio and
+      eccentricity (cell_shapes). skimage's regionprops is not a dependency: the measures are defined here, from
+      integer sums per component (second-order moments and three counts of boundary-pixel configurations:
+      shape_table / shape_table_np) turned into floats by one host function (region_shapes).
 
 Labels are canonical: 0 for background, else 1 + the raster index y*W + x (within the pixel's own image) of the first
 pixel of the component. That numbering does not depend on the algorithm, the batch or the run, so the device path
-(csrc/components.hip: adp_cc_label / adp_cc_areas / adp_cc_filter / adp_cc_table / adp_cc_relabel) and the numpy path
-below (label_np / areas_np / filter_np / table_np: hosts without a GPU, and the tests' reference) agree bit for bit.
+(csrc/components.hip: adp_cc_label / adp_cc_areas / adp_cc_filter / adp_cc_table / adp_cc_relabel / adp_cc_shape) and
+the numpy path below (label_np / areas_np / filter_np / table_np / shape_table_np: hosts without a GPU, and the tests'
+reference) agree bit for bit.
 Connectivity 8 is cv2's connectivity=8 and skimage's 2-D default; 4 is scipy.ndimage.label's default.
 
 cv2 and skimage are not dependencies, so parity with cv2.connectedComponentsWithStats and skimage.measure.label
@@ -25,6 +29,8 @@ SRC_U8, SRC_F32 = 0, 1
 # region of the kernels' in-LDS labelling stage (include/adipose_hip.h ADP_CC_REGION_ROWS / _COLS): the GPU tests place
 # their shapes around it
 REGION_ROWS, REGION_COLS = 32, 64
+# tile of the shape kernel, which reads a two-pixel halo around it (ADP_CC_SHAPE_TILE_ROWS / _COLS)
+SHAPE_TILE_ROWS, SHAPE_TILE_COLS = 64, 128
 MAX_PIXELS = 2 ** 31 - 2
 
 
@@ -192,6 +198,106 @@ def _int_bincount(k, val, rows):
     return acc
 
 
+# the perimeter codes counted by p_straight, p_diag and p_mixed, and what each contributes to the perimeter
+PERIMETER_CODES = ((5, 7, 15, 17, 25, 27), (21, 33), (13, 23))
+PERIMETER_WEIGHTS = (1.0, float(np.sqrt(2.0)), float((1.0 + np.sqrt(2.0)) / 2.0))
+
+
+def _check_moment_bound(H, W):
+    if H * W * (max(H, W) - 1) ** 2 >= 2 ** 63:
+        raise ValueError("H * W * (max(H, W) - 1)^2 is 2^63 or more (the moment sums are int64)")
+
+
+def shape_table_np(labels, max_rows):
+    """Canonical labels -> (N, max_rows, 8) int64 (2-D labels: without N), rows {first, S_xx, S_yy, S_xy, p_straight,
+    p_diag, p_mixed, border_px} in table_np's order and with its truncation. S_xx / S_yy / S_xy are the sums of x^2,
+    y^2 and x*y over the component's pixels (x the column, y the row). A border pixel has an edge neighbour outside its
+    component (another label, or outside the image); its code is 1 + 2 n4 + 10 nd, n4 / nd counting its edge / diagonal
+    neighbours that are border pixels of the same component; p_straight, p_diag and p_mixed count the codes in
+    PERIMETER_CODES, border_px all border pixels."""
+    lab, squeeze = _as3(labels)
+    N, H, W = lab.shape
+    _check_moment_bound(H, W)
+    out = np.zeros((N, max_rows, 8), np.int64)
+    for n in range(N):
+        L = lab[n].astype(np.int64)
+        v = L.ravel()
+        idx = np.flatnonzero(v)
+        firsts = np.unique(v[idx]) - 1
+        k = np.searchsorted(firsts, v[idx] - 1)
+        keep = k < max_rows
+        k, idx = k[keep], idx[keep]
+        rows = min(len(firsts), max_rows)
+        y, x = idx // W, idx % W
+        P = np.pad(L, 1)   # label 0 outside the image
+        border = (L != 0) & ((P[:-2, 1:-1] != L) | (P[2:, 1:-1] != L) | (P[1:-1, :-2] != L) | (P[1:-1, 2:] != L))
+        B = np.pad(np.where(border, L, -1), 1, constant_values=-1)   # the label of a border pixel, else no label
+        n4 = sum((B[dy:dy + H, dx:dx + W] == L).astype(np.int64) for dy, dx in ((0, 1), (2, 1), (1, 0), (1, 2)))
+        nd = sum((B[dy:dy + H, dx:dx + W] == L).astype(np.int64) for dy, dx in ((0, 0), (0, 2), (2, 0), (2, 2)))
+        code = np.where(border, 1 + 2 * n4 + 10 * nd, 0).ravel()[idx]
+        t = out[n]
+        t[:rows, 0] = firsts[:rows]
+        t[:rows, 1] = _int_bincount(k, x * x, rows)
+        t[:rows, 2] = _int_bincount(k, y * y, rows)
+        t[:rows, 3] = _int_bincount(k, x * y, rows)
+        for col, codes in enumerate(PERIMETER_CODES):
+            t[:rows, 4 + col] = _int_bincount(k, np.isin(code, codes), rows)
+        t[:rows, 7] = _int_bincount(k, code > 0, rows)
+    return out[0] if squeeze else out
+
+
+def region_shapes(table_rows, shape_rows):
+    """The float measures of components from their integer rows: table_rows (..., 8) as table / table_np give them and
+    shape_rows (..., 8) as shape_table / shape_table_np do, for the same components. A dict of float64 arrays of
+    shape (...): area, perimeter, circularity, major_axis_length, minor_axis_length, aspect_ratio, eccentricity,
+    centroid_x, centroid_y. Rows of area 0 (unused rows) give zeros.
+
+      perimeter = p_straight + sqrt(2) p_diag + (1 + sqrt(2)) / 2 p_mixed
+      circularity = 4 pi A / (P^2 + 1e-10), aspect_ratio = major / (minor + 1e-10)    (the reference's lines 113-114)
+      a = (A S_xx - S_x^2) / A^2, b = (A S_yy - S_y^2) / A^2, c = (A S_xy - S_x S_y) / A^2     (central moments)
+      d = sqrt(((a - b) / 2)^2 + c^2), l1 = (a + b) / 2 + d, l2 = max((a + b) / 2 - d, 0)
+      major / minor axis = 4 sqrt(l1) / 4 sqrt(l2), eccentricity = sqrt(1 - l2 / l1) (0 where l1 == 0)
+
+    The numerators A S_xx - S_x^2 and the like are formed in Python integers (A S_xx passes 2^63 for large
+    components) and divided once; both paths go through this function, so their floats are the same."""
+    t, s = np.asarray(table_rows, np.int64), np.asarray(shape_rows, np.int64)
+    if t.shape != s.shape or t.shape[-1] != 8:
+        raise ValueError("region_shapes takes table rows and shape rows of the same (..., 8) shape")
+    lead = t.shape[:-1]
+    t, s = t.reshape(-1, 8), s.reshape(-1, 8)
+    K = t.shape[0]
+    out = {k: np.zeros(K, np.float64) for k in ("area", "perimeter", "circularity", "major_axis_length",
+                                                "minor_axis_length", "aspect_ratio", "eccentricity", "centroid_x",
+                                                "centroid_y")}
+    a, b, c = np.zeros(K, np.float64), np.zeros(K, np.float64), np.zeros(K, np.float64)
+    for i in range(K):
+        A, Sx, Sy = int(t[i, 1]), int(t[i, 6]), int(t[i, 7])
+        if A <= 0:
+            continue
+        Sxx, Syy, Sxy = int(s[i, 1]), int(s[i, 2]), int(s[i, 3])
+        a[i] = (A * Sxx - Sx * Sx) / (A * A)   # int / int: one correctly rounded division
+        b[i] = (A * Syy - Sy * Sy) / (A * A)
+        c[i] = (A * Sxy - Sx * Sy) / (A * A)
+        out["centroid_x"][i], out["centroid_y"][i] = Sx / A, Sy / A
+    area = t[:, 1].astype(np.float64)
+    live = area > 0
+    per = PERIMETER_WEIGHTS[0] * s[:, 4] + PERIMETER_WEIGHTS[1] * s[:, 5] + PERIMETER_WEIGHTS[2] * s[:, 6]
+    per = np.where(live, per, 0.0)
+    d = np.sqrt(((a - b) / 2) ** 2 + c ** 2)
+    l1 = (a + b) / 2 + d
+    l2 = np.maximum((a + b) / 2 - d, 0.0)
+    major, minor = 4 * np.sqrt(l1), 4 * np.sqrt(l2)
+    ecc = np.zeros(K, np.float64)
+    nz = l1 > 0
+    ecc[nz] = np.sqrt(1 - l2[nz] / l1[nz])   # l2 <= l1, as d >= 0
+    out["area"], out["perimeter"] = np.where(live, area, 0.0), per
+    out["circularity"] = 4 * np.pi * out["area"] / (per ** 2 + 1e-10)
+    out["major_axis_length"], out["minor_axis_length"] = major, minor
+    out["aspect_ratio"] = major / (minor + 1e-10)
+    out["eccentricity"] = ecc
+    return {k: v.reshape(lead) for k, v in out.items()}
+
+
 def relabel_np(labels):
     """Canonical labels -> dense labels 1..K in raster order of first pixel (cv2's numbering), int32."""
     lab, squeeze = _as3(labels)
@@ -318,6 +424,21 @@ def table(labels, max_rows):
     with torch.cuda.device(lab.device):
         call("adp_cc_table", N, H, W, ptr(lab), max_rows, ptr(tab) if max_rows > 0 else None, ptr(counts), stream_ptr())
     return (tab[0], counts[0]) if lab.dim() == 2 else (tab, counts)
+
+
+def shape_table(labels, max_rows):
+    """Device labels -> (N, max_rows, 8) int64 device tensor (2-D labels: without N): shape_table_np's rows."""
+    import torch
+
+    from ._lib import call, ptr, stream_ptr
+    lab = _labels_arg(labels)
+    N, H, W = _nhw(lab)
+    _check_moment_bound(H, W)
+    max_rows = int(max_rows)
+    out = torch.empty((N, max_rows, 8), dtype=torch.int64, device=lab.device)
+    with torch.cuda.device(lab.device):
+        call("adp_cc_shape", N, H, W, ptr(lab), max_rows, ptr(out) if max_rows > 0 else None, stream_ptr())
+    return out[0] if lab.dim() == 2 else out
 
 
 def relabel(labels):
@@ -464,8 +585,7 @@ def cell_statistics(mask, min_area=10, threshold=0.5):
       areas             their areas, a list of floats in raster order of first pixel
       tissue_coverage   the share of pixels above the threshold (all of them, small regions included)
     An integer or bool mask is compared as the reference's float mask would be (1 > 0.5). The reference's perimeter,
-    circularity, aspect ratio and eccentricity are skimage regionprops quantities (moments and a boundary estimate
-    of skimage's own) and are left out."""
+    circularity, aspect ratio and eccentricity of the same cells are cell_shapes' part."""
     shape = tuple(mask.shape)
     if len(shape) != 2:
         raise ValueError("cell_statistics takes one (H, W) mask")
@@ -488,6 +608,70 @@ def cell_statistics(mask, min_area=10, threshold=0.5):
         total = int(a.sum())
     kept = a[a >= min_area]
     return {"num_cells": int(len(kept)), "areas": [float(v) for v in kept], "tissue_coverage": float(total / (H * W))}
+
+
+def cell_shapes(mask, min_area=10, threshold=0.5):
+    """The rest of analyze_cell_characteristics for one (H, W) mask: for the 8-connected components of mask > threshold
+    with at least min_area pixels, in raster order of first pixel, a dict with num_cells, areas, perimeters,
+    circularities, aspect_ratios, eccentricities (lists of floats, one entry per cell; region_shapes has the formulas)
+    and tissue_coverage (the share of pixels above the threshold). num_cells, areas and tissue_coverage are
+    cell_statistics' (stats_from_shapes). On the device: labels with the fused threshold, the table sized by a first
+    guess of 4096 rows and made once more when there are more components, the shape rows for the same row count, and
+    one copy of the K rows of both to the host."""
+    shape = tuple(mask.shape)
+    if len(shape) != 2:
+        raise ValueError("cell_shapes takes one (H, W) mask")
+    H, W = shape
+    if not _on_device(mask):
+        m = mask.numpy() if _is_tensor(mask) else np.asarray(mask)
+        lab = label_np(m > threshold, 8)
+        k = int(np.count_nonzero(areas_np(lab)))
+        tab, _ = table_np(lab, k)
+        shp = shape_table_np(lab, k)
+    else:
+        import torch
+        src = _to_device(mask)
+        if src.dtype != torch.float32:
+            src = src.to(torch.float32)
+        lab = label(src, 8, threshold=float(threshold))
+        rows = 4096
+        tab_d, cnt = table(lab, rows)
+        k = int(cnt.item())
+        if k > rows:
+            rows = k
+            tab_d, cnt = table(lab, rows)
+        both = torch.cat((tab_d[:k], shape_table(lab, rows)[:k]), dim=1).cpu().numpy()
+        tab, shp = both[:, :8], both[:, 8:]
+    r = region_shapes(tab, shp)
+    total = int(tab[:, 1].sum())
+    keep = r["area"] >= min_area
+
+    def kept(name):
+        return [float(v) for v in r[name][keep]]
+
+    return {"num_cells": int(keep.sum()), "areas": kept("area"), "perimeters": kept("perimeter"),
+            "circularities": kept("circularity"), "aspect_ratios": kept("aspect_ratio"),
+            "eccentricities": kept("eccentricity"), "tissue_coverage": float(total / (H * W))}
+
+
+def stats_from_shapes(shapes):
+    """cell_statistics' dict for the same mask and arguments, from cell_shapes' (a run that wants both labels once)."""
+    return {k: shapes[k] for k in ("num_cells", "areas", "tissue_coverage")}
+
+
+CELL_SHAPES_HEADER = ["name", "num_cells", "mean_perimeter", "median_perimeter", "mean_circularity", "median_circularity",
+                      "mean_aspect_ratio", "median_aspect_ratio", "mean_eccentricity", "median_eccentricity"]
+
+
+def cell_shapes_row(name, shapes=None):
+    """One row of cell_shapes.csv from cell_shapes' dict (None: the all-zero row of a tile that was not processed)."""
+    if not shapes or not shapes["num_cells"]:
+        return [name, 0] + ["0.0000"] * 8
+    row = [name, int(shapes["num_cells"])]
+    for key in ("perimeters", "circularities", "aspect_ratios", "eccentricities"):
+        v = np.asarray(shapes[key], np.float64)
+        row += [f"{v.mean():.4f}", f"{np.median(v):.4f}"]
+    return row
 
 
 CELL_STATS_HEADER = ["name", "num_cells", "mean_area", "median_area", "min_area", "max_area", "tissue_coverage"]

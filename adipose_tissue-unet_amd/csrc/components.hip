@@ -48,6 +48,29 @@
 // With overflow the bound is the number of wave runs of the label in the tile (at most 64 * 128).
 // adp_cc_table ranks the roots (labels[i] == i + 1) with an exclusive scan (hipcub) and accumulates straight into the
 // caller's rows {first, area, x_min, y_min, x_max, y_max, sum_x, sum_y}; a root's rank is its row.
+//
+// adp_cc_shape: the integer sums behind perimeter, axes and eccentricity, rows {first, S_xx, S_yy, S_xy, p_straight,
+// p_diag, p_mixed, border_px} in the table's order (the same scan). One launch of cc_shape_kernel, one block per tile
+// of ST_R x ST_C = 64 x 128 pixels:
+//   1. the tile's labels with a two-pixel halo go to LDS (0 outside the image): a pixel's perimeter code depends on the
+//      border flags of its eight neighbours, and each flag on that neighbour's four edge neighbours.
+//   2. every pixel of the tile and of the first halo ring whose label differs from one of its edge neighbours' gets
+//      the border flag, kept in bit 31 of its LDS word (labels are at most 2^31 - 1). The comparisons mask that bit, so
+//      the pass needs no second buffer and no barrier of its own.
+//   3. a wave takes 64 consecutive pixels of a row from LDS. A border pixel counts the neighbours whose word equals its
+//      own (same label and flagged): code = 1 + 2 * n4 + 10 * nd, classified by three bit masks. Runs of equal labels
+//      are aggregated by their first lane as in cc_accum_kernel: moments in closed form, relative to the tile, and the
+//      four perimeter counts as popcount(ballot(class) & run mask). The sums go into an LDS hash table of SHT = 512
+//      labels; after a barrier every occupied entry translates its moments to image coordinates in 64 bit and issues
+//      its global atomics once (zero counts are skipped). A run without a slot after PROBES probes goes to memory.
+//      The root pixel of a component stores `first`.
+// LDS: labels (64 + 4) * (128 + 4) * 4 = 35904 B, keys 2048 B, values 512 * 10 * 4 = 20480 B: 58432 B, two blocks
+// of 512 threads (16 waves) per CU of 160 KiB; a thread's 18 staging loads are issued together. The 64 x 256 tile of
+// the areas would need 70720 B for the labels alone.
+// Worst-case atomics per address (S_xx of one component) = tiles the component touches:
+//   all-foreground 1024^2:  (1024 / 64) * (1024 / 128)  =   128 adds   (~2 us at 17 ns)
+//   all-foreground 8192^2:  (8192 / 64) * (8192 / 128)  =  8192 adds   (~140 us)
+// twice the areas' count, the price of the smaller tile.
 #include <hipcub/hipcub.hpp>
 
 #include <climits>
@@ -338,6 +361,148 @@ __global__ __launch_bounds__(TPB) void cc_accum_kernel(int H, int W, int ntr, in
   }
 }
 
+// ---------------------------------------------------------------- shape sums per component
+constexpr int ST_R = ADP_CC_SHAPE_TILE_ROWS, ST_C = ADP_CC_SHAPE_TILE_COLS;   // tile of the shape sums
+constexpr int SP = ST_C + 4, SROWS = ST_R + 4;                               // the staged labels: pitch and rows
+constexpr int RING_C = ST_C + 2, RING = (ST_R + 2) * RING_C;                 // the tile and the first halo ring
+constexpr int SHT_BITS = 9, SHT = 1 << SHT_BITS;
+constexpr int SNV = 10;   // ints per LDS entry: {area, sum rx, sum ry, sum rx^2, sum ry^2, sum rx*ry, p_straight, p_diag, p_mixed, border_px}
+constexpr int SSEGS = ST_R * (ST_C / 64);
+constexpr int STPB = 512, SWAVES = STPB / 64;                   // eight waves a block: two blocks a CU by LDS, 16 waves
+constexpr int STAGE = (SROWS * SP + STPB - 1) / STPB;          // labels a thread stages: all its loads are in flight at once
+static_assert(ST_C % 64 == 0 && SSEGS % SWAVES == 0, "a wave takes 64 consecutive pixels of a tile row");
+// rx <= ST_C - 1 and ry <= ST_R - 1 are relative to the tile, so an entry's largest sum over all ST_R * ST_C pixels is
+// below 64 * 128 * 127^2 = 132'128'768 < 2^31: the LDS entries are 32 bit
+static_assert((long long)ST_R * ST_C * (ST_C - 1) * (ST_C - 1) < INT_MAX && (long long)ST_R * ST_C * (ST_R - 1) * (ST_R - 1) < INT_MAX,
+              "tile-relative moments must fit an int");
+constexpr int BORDER_BIT = INT_MIN;
+constexpr u64 code_mask(std::initializer_list<int> codes) {
+  u64 m = 0;
+  for (int c : codes) m |= 1ull << c;
+  return m;
+}
+constexpr u64 CODES_STRAIGHT = code_mask({5, 7, 15, 17, 25, 27}), CODES_DIAG = code_mask({21, 33}), CODES_MIXED = code_mask({13, 23});
+
+// q: an entry's SNV sums, relative to the tile at (x0, y0)
+ADP_DEV void shape_emit(const int* rank, int max_rows, long long* rows, int lab, int x0, int y0, const int* q) {
+  const int k = rank[lab - 1] - rank[0];
+  if (k >= max_rows) return;
+  u64* row = reinterpret_cast<u64*>(rows + (size_t)k * 8);
+  const long long a = q[0], sx = q[1], sy = q[2], X = x0, Y = y0;
+  // sum (X + rx)^2 = sum rx^2 + 2 X sum rx + X^2 a, and likewise: every term is at most the image's sum, which fits
+  atomicAdd(&row[1], (u64)(q[3] + 2 * X * sx + X * X * a));
+  atomicAdd(&row[2], (u64)(q[4] + 2 * Y * sy + Y * Y * a));
+  atomicAdd(&row[3], (u64)(q[5] + X * sy + Y * sx + X * Y * a));
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+    if (q[6 + j]) atomicAdd(&row[4 + j], (u64)q[6 + j]);
+}
+
+__global__ __launch_bounds__(STPB) void cc_shape_kernel(int H, int W, int ntr, int ntc, const int* __restrict__ labels,
+                                                       const int* __restrict__ rank, int max_rows, long long* shape) {
+  __shared__ int S[SROWS * SP];
+  __shared__ int keys[SHT];
+  __shared__ int vals[SHT * SNV];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int per = ntr * ntc;
+  const int n = blockIdx.x / per, rem = blockIdx.x - n * per;
+  const int y0 = (rem / ntc) * ST_R, x0 = (rem % ntc) * ST_C;
+  const size_t hw = (size_t)H * W;
+  const int* L = labels + n * hw;
+  const int* rk = rank + n * hw;
+  long long* rows = shape + (size_t)n * max_rows * 8;
+  int staged[STAGE];
+#pragma unroll
+  for (int i = 0; i < STAGE; ++i) {
+    const int e = threadIdx.x + i * STPB, y = y0 - 2 + e / SP, x = x0 - 2 + e % SP;
+    // an unconditional load from the clamped position and no control flow (&, not &&): under a branch per load each
+    // load waits for the one before
+    const int v = L[(size_t)min(max(y, 0), H - 1) * W + min(max(x, 0), W - 1)];
+    const bool inside = (e < SROWS * SP) & (y >= 0) & (y < H) & (x >= 0) & (x < W);
+    staged[i] = inside ? v : 0;
+  }
+  for (int e = threadIdx.x; e < SHT; e += STPB) keys[e] = 0;
+  for (int e = threadIdx.x; e < SHT * SNV; e += STPB) vals[e] = 0;
+#pragma unroll
+  for (int i = 0; i < STAGE; ++i) {
+    const int e = threadIdx.x + i * STPB;
+    if (e < SROWS * SP) S[e] = staged[i];
+  }
+  __syncthreads();
+
+  // border flags of the tile and the first ring. Another thread may set the bit of a word while this one compares it:
+  // the comparison masks the bit, so either value gives the same answer
+  for (int e = threadIdx.x; e < RING; e += STPB) {
+    int* c = &S[(e / RING_C + 1) * SP + e % RING_C + 1];
+    const int v = __hip_atomic_load(c, RLX_WG) & INT_MAX;
+    if (v == 0) continue;
+    auto differs = [v](const int* p) { return (__hip_atomic_load(p, RLX_WG) & INT_MAX) != v; };
+    if (differs(c - SP) || differs(c + SP) || differs(c - 1) || differs(c + 1)) __hip_atomic_store(c, v | BORDER_BIT, RLX_WG);
+  }
+  __syncthreads();
+
+  for (int s = wave; s < SSEGS; s += SWAVES) {
+    const int ry = s / (ST_C / 64), rx = (s % (ST_C / 64)) * 64 + lane;
+    const int* c = &S[(ry + 2) * SP + rx + 2];
+    const int w = c[0], v = w & INT_MAX;   // 0 outside the image
+    if (__ballot(v != 0) == 0) continue;
+    const bool border = w < 0;
+    u64 cls = 0;
+    if (border) {
+      const int n4 = (c[-SP] == w) + (c[SP] == w) + (c[-1] == w) + (c[1] == w);
+      const int nd = (c[-SP - 1] == w) + (c[-SP + 1] == w) + (c[SP - 1] == w) + (c[SP + 1] == w);
+      cls = 1ull << (1 + 2 * n4 + 10 * nd);
+    }
+    const u64 bb = __ballot(border), bs = __ballot((cls & CODES_STRAIGHT) != 0), bd = __ballot((cls & CODES_DIAG) != 0),
+              bm = __ballot((cls & CODES_MIXED) != 0);
+    const int prev = __shfl_up(v, 1, 64);
+    const bool change = lane == 0 || prev != v;
+    const u64 cb = __ballot(change);
+    if (v == 0) continue;
+    const int idx = (y0 + ry) * W + x0 + rx;   // inside the image, as v != 0
+    if (v == idx + 1) {                        // the component's first pixel: its row's constant part
+      const int k = rk[idx] - rk[0];
+      if (k < max_rows) rows[(size_t)k * 8] = idx;
+    }
+    if (!change) continue;
+    const u64 nx = lane == 63 ? 0ull : cb >> (lane + 1);
+    const int len = nx ? __ffsll((long long)nx) : 64 - lane;   // up to the next change or the end of the wave
+    const u64 run = (len == 64 ? ~0ull : (1ull << len) - 1) << lane;
+    const int t = len * (len - 1) / 2;                          // sum of 0 .. len - 1
+    int q[SNV];
+    q[0] = len;
+    q[1] = len * rx + t;
+    q[2] = len * ry;
+    q[3] = len * rx * rx + 2 * rx * t + t * (2 * len - 1) / 3;   // sum of squares of 0 .. len - 1 = t (2 len - 1) / 3
+    q[4] = len * ry * ry;
+    q[5] = ry * q[1];
+    q[6] = __popcll(bs & run);
+    q[7] = __popcll(bd & run);
+    q[8] = __popcll(bm & run);
+    q[9] = __popcll(bb & run);
+    uint32_t h = ((uint32_t)v * 2654435761u) >> (32 - SHT_BITS);
+    int slot = -1;
+    for (int p = 0; p < PROBES; ++p) {
+      const int old = atomicCAS(&keys[h], 0, v);
+      if (old == 0 || old == v) { slot = (int)h; break; }
+      h = (h + 1) & (SHT - 1);
+    }
+    if (slot >= 0) {
+      int* e = &vals[slot * SNV];
+#pragma unroll
+      for (int j = 0; j < SNV; ++j)
+        if (q[j]) atomicAdd(&e[j], q[j]);
+    } else {
+      shape_emit(rk, max_rows, rows, v, x0, y0, q);
+    }
+  }
+  __syncthreads();
+  for (int e = threadIdx.x; e < SHT; e += STPB) {
+    const int v = keys[e];
+    if (v != 0) shape_emit(rk, max_rows, rows, v, x0, y0, &vals[e * SNV]);
+  }
+}
+
 __global__ __launch_bounds__(TPB) void cc_filter_kernel(size_t hw, size_t total, const int* __restrict__ labels,
                                                         const int* __restrict__ area, int min_px, uint8_t* out_u8,
                                                         float* out_f32) {
@@ -500,6 +665,33 @@ extern "C" int adp_cc_table(int N, int H, int W, const int* labels, int max_rows
                          (int*)nullptr, rank, max_rows, tab);
   }
   return adp::check_launch("adp_cc_table");
+}
+
+extern "C" int adp_cc_shape(int N, int H, int W, const int* labels, int max_rows, long long* shape, adp_stream_t st) {
+  ADP_REQUIRE(labels, "adp_cc_shape: labels must be non-null");
+  ADP_REQUIRE(max_rows >= 0 && (shape || max_rows == 0), "adp_cc_shape: max_rows rows need a shape table");
+  if (!shape_ok("adp_cc_shape", N, H, W)) return -1;
+  // sum x^2 <= H * W * (W - 1)^2 and the like must fit int64; (max - 1)^2 < 2^62 as max < 2^31
+  const long long last = (long long)std::max(H, W) - 1, last2 = last * last;
+  ADP_REQUIRE(last2 == 0 || (long long)H * W <= LLONG_MAX / last2,
+              "adp_cc_shape: H * W * (max(H, W) - 1)^2 is 2^63 or more (the moment sums are int64)");
+  if (max_rows == 0) return 0;
+  const int ntr = (H + ST_R - 1) / ST_R, ntc = (W + ST_C - 1) / ST_C;
+  const int G = scan_group(N, H, W);
+  ADP_REQUIRE((long long)G * ntr * ntc <= 0x7FFFFFFFll, "adp_cc_shape: too many blocks (H * W too large for one launch)");
+  hipStream_t s = (hipStream_t)st;
+  const size_t hw = (size_t)H * W;
+  ADP_REQUIRE(hipMemsetAsync(shape, 0, (size_t)N * max_rows * 8 * sizeof(long long), s) == hipSuccess,
+              "adp_cc_shape: memset failed");
+  for (int n0 = 0; n0 < N; n0 += G) {
+    const int g = std::min(G, N - n0);
+    const int* lab = labels + (size_t)n0 * hw;
+    const int* rank = scan_roots("adp_cc_shape", g, hw, lab, s);
+    if (!rank) return -2;
+    hipLaunchKernelGGL(cc_shape_kernel, dim3((unsigned)(g * ntr * ntc)), dim3(STPB), 0, s, H, W, ntr, ntc, lab, rank, max_rows,
+                       shape + (size_t)n0 * max_rows * 8);
+  }
+  return adp::check_launch("adp_cc_shape");
 }
 
 extern "C" int adp_cc_relabel(int N, int H, int W, const int* labels, int* dense, adp_stream_t st) {

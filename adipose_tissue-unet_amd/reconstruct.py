@@ -325,10 +325,14 @@ def _component_settings(args):
     """The connected-component settings of a run, for the log: nothing when neither is set (the log of a run without
     them is what it was)."""
     min_cc, stats = int(getattr(args, "min_cc_px", 0) or 0), bool(getattr(args, "cell_stats", False))
-    if min_cc <= 0 and not stats:
+    shapes = bool(getattr(args, "cell_shapes", False))
+    if min_cc <= 0 and not stats and not shapes:
         return {}
-    return {"min_cc_px": min_cc, "cell_stats": stats,
-            "cell_min_area": int(getattr(args, "cell_min_area", 10)) if stats else None}
+    out = {"min_cc_px": min_cc, "cell_stats": stats,
+           "cell_min_area": int(getattr(args, "cell_min_area", 10)) if stats or shapes else None}
+    if shapes:   # only then: the settings of a run without the flag are what they were
+        out["cell_shapes"] = True
+    return out
 
 
 def reconstruct_all_slides(args, model=None, process_group=None):
@@ -337,10 +341,12 @@ def reconstruct_all_slides(args, model=None, process_group=None):
     args.min_cc_px > 0 (build_dataset.py's --min-cc-px): the slide prediction is thresholded on the device and its
     8-connected components of fewer than min_cc_px pixels are removed (components.py); the 0 / 1 mask takes the
     prediction's place in prediction_mask.tif, the overlays and the metrics. args.cell_stats: cell_stats.csv with one
-    row per slide, from the mask that is written."""
+    row per slide, from the mask that is written; args.cell_shapes: cell_shapes.csv, likewise (with both, the mask is
+    labelled once)."""
     min_cc_px, cell_stats = int(getattr(args, "min_cc_px", 0) or 0), bool(getattr(args, "cell_stats", False))
-    post = min_cc_px > 0 or cell_stats
-    cell_rows = []
+    cell_shapes = bool(getattr(args, "cell_shapes", False))
+    post = min_cc_px > 0 or cell_stats or cell_shapes
+    cell_rows, shape_rows = [], []
     print(f"\n{'=' * 80}\nFULL IMAGE RECONSTRUCTION FROM OVERLAPPING TILES\n{'=' * 80}")
     set_deterministic_seeds(1337)
     data_root = Path(args.data_root)
@@ -398,8 +404,14 @@ def reconstruct_all_slides(args, model=None, process_group=None):
                 lab = cc.label(full_pred, 8, threshold=float(args.threshold))
                 full_pred = cc.filter_small(lab, cc.areas(lab), min_cc_px, torch.float32)
                 del lab
-            if cell_stats:
+            st = None
+            if cell_shapes:
+                sh = cc.cell_shapes(full_pred, int(getattr(args, "cell_min_area", 10)), float(args.threshold))
+                shape_rows.append(cc.cell_shapes_row(slide_id, sh))
+                st = cc.stats_from_shapes(sh)
+            elif cell_stats:
                 st = cc.cell_statistics(full_pred, int(getattr(args, "cell_min_area", 10)), float(args.threshold))
+            if cell_stats:
                 cell_rows.append(cc.cell_stats_row(slide_id, st))
                 print(f"  Cells: {st['num_cells']} (coverage {st['tissue_coverage']:.1%})")
             full_rgb, full_pred = full_rgb.cpu().numpy(), full_pred.cpu().numpy()
@@ -452,6 +464,14 @@ def reconstruct_all_slides(args, model=None, process_group=None):
             w = csv.writer(f)
             w.writerow(CELL_STATS_HEADER)
             w.writerows(cell_rows)
+    if cell_shapes and rank0:
+        import csv
+
+        from .components import CELL_SHAPES_HEADER
+        with open(output_dir / "cell_shapes.csv", "w", newline="") as f:
+            w = csv.writer(f)
+            w.writerow(CELL_SHAPES_HEADER)
+            w.writerows(shape_rows)
     if results and rank0:
         rows = [{"slide_id": r["slide_id"], "dice_score": r["metrics"]["dice_score"],
                  "jaccard_iou": r["metrics"]["jaccard_index"], "sensitivity": r["metrics"]["sensitivity"],

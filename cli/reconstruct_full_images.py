@@ -42,6 +42,9 @@ def build_parser():
     c.add_argument("--cell-stats", action="store_true", default=False,
                    help="write cell_stats.csv: per slide num_cells, mean / median / min / max area, tissue_coverage")
     c.add_argument("--cell-min-area", type=int, default=10, help="regions below this area are not counted as cells")
+    c.add_argument("--cell-shapes", action="store_true", default=False,
+                   help="write cell_shapes.csv: per slide num_cells, mean / median perimeter, circularity, aspect ratio "
+                        "and eccentricity of the cells (--cell-min-area)")
     return p
 
 

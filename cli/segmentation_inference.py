@@ -96,6 +96,9 @@ def build_parser():
                    help="write cell_stats.csv: per image num_cells, mean / median / min / max area, tissue_coverage "
                         "of the mask that is written")
     c.add_argument("--cell-min-area", type=int, default=10, help="regions below this area are not counted as cells")
+    c.add_argument("--cell-shapes", action="store_true", default=False,
+                   help="write cell_shapes.csv: per image num_cells, mean / median perimeter, circularity, aspect ratio "
+                        "and eccentricity of the cells (--cell-min-area) of the mask that is written")
     return p
 
 
@@ -157,12 +160,13 @@ def main(argv=None):
         from adipose_amd.quality import CLASSES, TileQC, measures
         qc = TileQC(args.white_threshold, args.white_ratio_limit, args.blurry_threshold)
     raw_rgb = normalizer is not None or qc is not None
-    cell_rows = []
-    if args.min_cc_px > 0 or args.cell_stats:
+    cell_rows, shape_rows = [], []
+    if args.min_cc_px > 0 or args.cell_stats or args.cell_shapes:
         import torch
 
-        from adipose_amd.components import (CELL_STATS_HEADER, cell_statistics, cell_stats_row,
-                                            remove_small_components)
+        from adipose_amd.components import (CELL_SHAPES_HEADER, CELL_STATS_HEADER, cell_shapes, cell_shapes_row,
+                                            cell_statistics, cell_stats_row, remove_small_components,
+                                            stats_from_shapes)
 
     image_files = [f for f in images_dir.iterdir() if f.suffix.lower() in IMAGE_EXTS and f.is_file()]
     if not image_files:
@@ -205,12 +209,19 @@ def main(argv=None):
         if skipped:   # all background: nothing to label
             if args.cell_stats:
                 cell_rows.append(cell_stats_row(img_path.name))
-        elif args.min_cc_px > 0 or args.cell_stats:
+            if args.cell_shapes:
+                shape_rows.append(cell_shapes_row(img_path.name))
+        elif args.min_cc_px > 0 or args.cell_stats or args.cell_shapes:
             mask_dev = torch.from_numpy(binary).cuda()
             if args.min_cc_px > 0:
                 mask_dev = remove_small_components(mask_dev, args.min_cc_px)
                 binary = mask_dev.cpu().numpy()
-            if args.cell_stats:
+            if args.cell_shapes:   # its dict holds the statistics too: with both flags the mask is labelled once
+                shapes = cell_shapes(mask_dev, args.cell_min_area, 0.5)
+                shape_rows.append(cell_shapes_row(img_path.name, shapes))
+                if args.cell_stats:
+                    cell_rows.append(cell_stats_row(img_path.name, stats_from_shapes(shapes)))
+            elif args.cell_stats:
                 cell_rows.append(cell_stats_row(img_path.name, cell_statistics(mask_dev, args.cell_min_area, 0.5)))
         write_mask(masks_dir / f"{img_path.stem}_mask.tif", binary)
         if args.save_overlays:
@@ -230,6 +241,12 @@ def main(argv=None):
             w = csv.writer(f)
             w.writerow(CELL_STATS_HEADER)
             w.writerows(cell_rows)
+    if args.cell_shapes:
+        import csv
+        with open(output_dir / "cell_shapes.csv", "w", newline="") as f:
+            w = csv.writer(f)
+            w.writerow(CELL_SHAPES_HEADER)
+            w.writerows(shape_rows)
     print(f"\n{'=' * 80}\nINFERENCE COMPLETE\n{'=' * 80}")
     print(f"Processed: {len(image_files)} images")
     print(f"Time: {elapsed:.1f}s ({elapsed / len(image_files):.2f}s per image)")

@@ -474,6 +474,20 @@ int adp_cc_table(int N, int H, int W, const int* labels, int max_rows, long long
 /* dense (N, H, W) int32: 0 for background, else 1 + the row of the pixel's component in adp_cc_table's order
  * (labels 1..K in raster order of first pixel, as cv2 numbers them) */
 int adp_cc_relabel(int N, int H, int W, const int* labels, int* dense, adp_stream_t s);
+/* tile of adp_cc_shape's kernel (tests place their shapes around it; the kernel reads a two-pixel halo around it) */
+#define ADP_CC_SHAPE_TILE_ROWS 64
+#define ADP_CC_SHAPE_TILE_COLS 128
+/* the integer sums behind analyze_cell_characteristics' perimeter, circularity, aspect ratio and eccentricity.
+ * shape (N, max_rows, 8) int64, rows {first, S_xx, S_yy, S_xy, p_straight, p_diag, p_mixed, border_px} in
+ * adp_cc_table's order and with its truncation (components beyond max_rows dropped, unused rows zero). S_xx = sum x^2,
+ * S_yy = sum y^2, S_xy = sum x*y over the component's pixels (x the column, y the row). A border pixel has an edge
+ * neighbour that is not in its component (another label, or outside the image); its code is 1 + 2*n4 + 10*nd with n4 /
+ * nd its edge / diagonal neighbours that are border pixels of the same component. p_straight counts the codes
+ * {5, 7, 15, 17, 25, 27}, p_diag {21, 33}, p_mixed {13, 23}, border_px all border pixels; perimeter = p_straight +
+ * sqrt(2)*p_diag + (1 + sqrt(2))/2*p_mixed. Stream-ordered, no synchronisation. Fails (message, nothing launched) on a
+ * NULL pointer (shape may be NULL only with max_rows = 0, which does nothing), max_rows < 0, a shape the other calls
+ * refuse, or H*W*(max(H, W) - 1)^2 >= 2^63 (the moment sums are int64) */
+int adp_cc_shape(int N, int H, int W, const int* labels, int max_rows, long long* shape, adp_stream_t s);
 
 /* ---- optimizer (Keras Adam / AdamW, :800-806) --------------------------------------------- */
 int adp_adam(size_t n, float* param, const float* grad, float* m, float* v, float lr, float beta1,

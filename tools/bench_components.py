@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Microbenchmark of the connected-component calls (csrc/components.hip): label, areas, filter and table, HIP-event
+"""Microbenchmark of the connected-component calls (csrc/components.hip): label, areas, filter, table and shape, HIP-event
 timed on warm calls, at (8, 1024, 1024) and (1, 8192, 8192), for adipocyte masks (data.synthetic_tile; the 8192^2 map
 is 8 x 8 different 1024^2 tiles side by side) and the contention / chain-length worst cases: all-foreground, the
 4-connected checkerboard and the one-pixel serpentine. One JSON line per size and mask with the median over rounds of
@@ -77,6 +77,7 @@ def main():
                 "areas": lambda: cc.areas(lab),
                 "filter": lambda: cc.filter_small(lab, area, args.min_px),
                 "table": lambda: cc.table(lab, args.max_rows),
+                "shape": lambda: cc.shape_table(lab, args.max_rows),
             }
             res = {k: [] for k in calls}
             for _ in range(args.rounds):
@@ -102,6 +103,7 @@ def main():
             line["label_filter_over_floor"] = round((line["label_us"] + line["filter_us"]) / line["floor_us"], 2)
             if name == "ones":   # atomics issued per address by the areas call: one per tile of 64 x 256 of an image
                 line["area_atomics_per_address"] = -(-H // 64) * -(-W // 256)
+                line["shape_atomics_per_address"] = -(-H // cc.SHAPE_TILE_ROWS) * -(-W // cc.SHAPE_TILE_COLS)
             if not args.no_scipy:
                 try:
                     import scipy.ndimage as ndi
