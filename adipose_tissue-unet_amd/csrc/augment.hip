@@ -315,7 +315,8 @@ extern "C" int adp_aug_remap(int H, int W, const float* src, const float* msrc, 
   return adp::check_launch("adp_aug_remap");
 }
 
-// work: >= 16 + 4*2048*4 bytes of device scratch (SelState + histograms), caller-owned
+// work: >= 64 + 4*2048*4 bytes of device scratch (SelState in the first 64 bytes, the histograms behind it),
+// caller-owned
 extern "C" int adp_percentile_normalize(size_t n, const float* src, float* dst, double p_low, double p_high,
                                         void* work, float* p_out, adp_stream_t st) {
   ADP_REQUIRE(n > 0 && src && dst && work && p_low >= 0 && p_high <= 100 && p_low <= p_high,

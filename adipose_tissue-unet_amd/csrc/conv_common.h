@@ -257,8 +257,9 @@ ADP_DEV bf16x8 tr_frag_sw(const unsigned char* base, int row0, int col0, int lan
 // `tile` holds `rows` x BN f32 accumulators (row stride BN + 4) for output pixels m0.. and GEMM
 // columns n0..; NTH threads each own one 8-column group (cg = tid % (BN/8)) and walk the rows.
 // Applies bias, ReLU, dropout, the pixel-shuffle / split / addend / mask / accumulate store modes
-// and collects per-channel partial sums into bs/bq: BatchNorm statistics (sum, sum of squares) of the
-// stored values, or with bnr_z the BatchNorm-backward sums (db, db*xhat) of the stored gradient.
+// and collects per-channel partial sums into bs/bq: BatchNorm statistics (sum, sum of squares) of the f32
+// value BEFORE the store's rounding (every kernel's convention, pinned by tests/test_gpu_conv_exact.py), or
+// with bnr_z (epi_rows_bnr) the BatchNorm-backward sums (db, db*xhat) of the stored, rounded gradient.
 // F8: fp8 launch — acc * wscale[n] before the bias, fp8 or bf16 store (compiled only into the fp8
 // kernels, so the bf16 kernels keep their register budget)
 template <int NTH, int BN, bool F8 = false, typename TO = bf16>

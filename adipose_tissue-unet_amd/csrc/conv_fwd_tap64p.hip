@@ -12,7 +12,9 @@
 // (accumulators -> LDS -> 16-B stores, two row groups, four barriers) with the MFMA pipe idle: 5-17 % of
 // a 3x3 layer at K = 9216..2304 and 40-75 % of a ConvTranspose forward (K = 128..1024).
 // Epilogue forms: plain / pixel-shuffle (ConvTranspose) / channel-split store, bias, ReLU, BatchNorm
-// statistics of the stored values (bn_sum), fused BatchNorm-backward reduction (BNR); every other epilogue
+// statistics (bn_sum: of the f32 value before the store's rounding, as in every other kernel; per tile and channel
+// quad a lane sums its 2 * MIQ rows in f32, row16_sum adds the 16 pixel lanes, everything after that is f64),
+// fused BatchNorm-backward reduction (BNR: of the stored, rounded gradient); every other epilogue
 // term (addend, mask, accumulate, dropout, fp8) stays on the non-persistent kernel.
 #include "conv_common.h"
 
