@@ -125,6 +125,9 @@ _SIGS = {
     "adp_cc_table": [_I, _I, _I, _P, _I, _P, _P, _P],
     "adp_cc_relabel": [_I, _I, _I, _P, _P, _P],
     "adp_cc_shape": [_I, _I, _I, _P, _I, _P, _P],
+    "adp_morph_pack": [_I, _I, _I, _P, _I, _F, _P, _P],
+    "adp_morph_bits": [_I, _I, _I, _P, _P, _I, C.POINTER(C.c_int), C.POINTER(C.c_int), _I, _P],
+    "adp_morph_unpack": [_I, _I, _I, _P, _P, _P, _P],
     "adp_create": [_P, _I, _P],
     "adp_destroy": [_P],
     "adp_param_size": [_P, C.c_char_p, _I, C.POINTER(C.c_size_t)],

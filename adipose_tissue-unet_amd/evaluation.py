@@ -506,11 +506,13 @@ def run_publication_evaluation(val_data_root: str, weights_path: str, output_dir
                                use_boundary_refine: bool = False, refine_kernel: int = 5,
                                adaptive_threshold: bool = False, save_overlays: bool = False, n_positive: int = 120,
                                n_negative: int = 30, *, tile_size: int = 1024, dtype: str = "f32",
-                               max_batch: int = 8, min_cc_px: int = 0) -> ComprehensiveMetrics:
+                               max_batch: int = 8, min_cc_px: int = 0,
+                               morph_close_k: int = 0) -> ComprehensiveMetrics:
     """:1446-1958 (same steps, prints and output files). tile_size / dtype / max_batch: this build. min_cc_px > 0:
     the pixel metrics are computed on the binarised prediction without its 8-connected components of fewer than
     min_cc_px pixels (components.remove_small_components, the treatment the ground-truth masks were built with);
-    0 leaves every number as it is."""
+    0 leaves every number as it is. morph_close_k > 0: the binarised prediction is first closed with the k x k ellipse
+    (morphology.morph_close, the step before it in the reference's builders); 0 likewise changes nothing."""
     import pandas as pd
 
     from .predictor import AdiposeUNet, SlidingWindowInference
@@ -589,15 +591,22 @@ def run_publication_evaluation(val_data_root: str, weights_path: str, output_dir
         slides[extract_slide_id(p)].append(i)
     n_slides = len(slides)
     print(f"✓ Grouped {n_files} tiles into {n_slides} slides")
+    if morph_close_k > 0:
+        from .morphology import morph_close
+        print(f"✓ Masks are closed with a {morph_close_k} x {morph_close_k} ellipse before the pixel metrics")
     if min_cc_px > 0:
         from .components import remove_small_components
         print(f"✓ Components below {min_cc_px} px are removed before the pixel metrics")
 
     def metric_pred(i):
-        if min_cc_px <= 0:
+        if min_cc_px <= 0 and morph_close_k <= 0:
             return preds[i]
         binary = (preds[i] > optimal_threshold).astype(np.uint8)
-        return remove_small_components(binary, min_cc_px).astype(np.float32)   # 1 > threshold, 0 is not
+        if morph_close_k > 0:
+            binary = morph_close(binary, morph_close_k)
+        if min_cc_px > 0:
+            binary = remove_small_components(binary, min_cc_px)
+        return binary.astype(np.float32)   # 1 > threshold, 0 is not
 
     print(f"\nCalculating slide-level metrics with threshold {optimal_threshold:.2f}...")
     keys = ["dice_scores", "jaccard_indices", "sensitivities", "specificities", "precisions", "f1_scores",

@@ -326,18 +326,24 @@ def _component_settings(args):
     them is what it was)."""
     min_cc, stats = int(getattr(args, "min_cc_px", 0) or 0), bool(getattr(args, "cell_stats", False))
     shapes = bool(getattr(args, "cell_shapes", False))
-    if min_cc <= 0 and not stats and not shapes:
+    close_k = int(getattr(args, "morph_close_k", 0) or 0)
+    if min_cc <= 0 and not stats and not shapes and close_k <= 0:
         return {}
     out = {"min_cc_px": min_cc, "cell_stats": stats,
            "cell_min_area": int(getattr(args, "cell_min_area", 10)) if stats or shapes else None}
     if shapes:   # only then: the settings of a run without the flag are what they were
         out["cell_shapes"] = True
+    if close_k > 0:   # likewise
+        out["morph_close_k"] = close_k
     return out
 
 
 def reconstruct_all_slides(args, model=None, process_group=None):
     """:586-866 — per slide: coverage check, dimensions, reconstruction, TIFF / PNG / metrics outputs.
     ``model`` overrides building AdiposeUNet from args.weights (tests, custom predictors).
+    args.morph_close_k > 0 (build_dataset.py's --morph-close-k): the slide prediction is thresholded into a bit-packed
+    plane on the device and closed with the k x k ellipse (morphology.py) before anything below; the 0 / 1 mask takes
+    the prediction's place.
     args.min_cc_px > 0 (build_dataset.py's --min-cc-px): the slide prediction is thresholded on the device and its
     8-connected components of fewer than min_cc_px pixels are removed (components.py); the 0 / 1 mask takes the
     prediction's place in prediction_mask.tif, the overlays and the metrics. args.cell_stats: cell_stats.csv with one
@@ -345,7 +351,10 @@ def reconstruct_all_slides(args, model=None, process_group=None):
     labelled once)."""
     min_cc_px, cell_stats = int(getattr(args, "min_cc_px", 0) or 0), bool(getattr(args, "cell_stats", False))
     cell_shapes = bool(getattr(args, "cell_shapes", False))
-    post = min_cc_px > 0 or cell_stats or cell_shapes
+    morph_close_k = int(getattr(args, "morph_close_k", 0) or 0)
+    if not 0 <= morph_close_k <= 63:
+        raise ValueError("morph_close_k must be in 0..63")
+    post = min_cc_px > 0 or cell_stats or cell_shapes or morph_close_k > 0
     cell_rows, shape_rows = [], []
     print(f"\n{'=' * 80}\nFULL IMAGE RECONSTRUCTION FROM OVERLAPPING TILES\n{'=' * 80}")
     set_deterministic_seeds(1337)
@@ -400,6 +409,10 @@ def reconstruct_all_slides(args, model=None, process_group=None):
             continue
         if post:   # the 64 M-pixel planes are still on the device
             from . import components as cc
+            if morph_close_k > 0:   # threshold -> close -> small components -> statistics
+                from . import morphology
+                full_pred = morphology.close(full_pred, morph_close_k, threshold=float(args.threshold),
+                                             dtype=torch.float32)
             if min_cc_px > 0:
                 lab = cc.label(full_pred, 8, threshold=float(args.threshold))
                 full_pred = cc.filter_small(lab, cc.areas(lab), min_cc_px, torch.float32)

@@ -36,6 +36,9 @@ def build_parser():
     p.add_argument("--tile", type=int, default=1024, help="tile size the network is built for (reference: 1024)")
     p.add_argument("--dtype", type=str, default="f32", choices=["f32", "bf16"])
     p.add_argument("--batch", type=int, default=8, help="tiles x TTA views per batched forward")
+    p.add_argument("--morph-close-k", type=int, default=0, choices=range(0, 64), metavar="K",
+                   help="close the binarised prediction with a K x K ellipse before --min-cc-px and the pixel metrics "
+                        "(build_dataset.py --morph-close-k; 0 = off, 1..63)")
     p.add_argument("--min-cc-px", type=int, default=0,
                    help="remove 8-connected components below this many pixels from the binarised prediction before the "
                         "pixel metrics (build_dataset.py --min-cc-px; 0 = off)")
@@ -93,7 +96,7 @@ def main(argv=None):
             use_boundary_refine=args.boundary_refine, refine_kernel=args.refine_kernel,
             adaptive_threshold=args.adaptive_threshold, save_overlays=args.save_overlays,
             n_positive=args.n_positive, n_negative=args.n_negative, tile_size=args.tile, dtype=args.dtype,
-            max_batch=args.batch, min_cc_px=args.min_cc_px)
+            max_batch=args.batch, min_cc_px=args.min_cc_px, morph_close_k=args.morph_close_k)
     except Exception as e:  # noqa: BLE001 (reference prints the failure and returns 1, :2201-2215)
         import traceback
         print(f"\n{'=' * 80}\n❌ EVALUATION FAILED\n{'=' * 80}\nError: {e}")

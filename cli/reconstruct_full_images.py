@@ -36,6 +36,9 @@ def build_parser():
     p.add_argument("--dtype", type=str, default="f32", choices=["f32", "bf16"])
     p.add_argument("--batch", type=int, default=8)
     c = p.add_argument_group("connected components (on the device, on the whole-slide mask)")
+    c.add_argument("--morph-close-k", type=int, default=0, choices=range(0, 64), metavar="K",
+                   help="close the thresholded slide mask with a K x K ellipse before anything else is done with it "
+                        "(build_dataset.py --morph-close-k; 0 = off, 1..63)")
     c.add_argument("--min-cc-px", type=int, default=0,
                    help="remove 8-connected components below this many pixels from the thresholded slide mask "
                         "(build_dataset.py --min-cc-px; 0 = off); the mask, the overlays and the metrics then use it")

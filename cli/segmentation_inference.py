@@ -89,6 +89,9 @@ def build_parser():
     q.add_argument("--skip-blurry", action="store_true", default=False,
                    help="skip blurry tiles too (default: only empty ones, as the reference keeps blurry tiles)")
     c = p.add_argument_group("connected components (on the device)")
+    c.add_argument("--morph-close-k", type=int, default=0, choices=range(0, 64), metavar="K",
+                   help="close the binarised mask with a K x K ellipse before anything else is done with it "
+                        "(build_dataset.py --morph-close-k; 0 = off, 1..63)")
     c.add_argument("--min-cc-px", type=int, default=0,
                    help="remove 8-connected components below this many pixels from the binarised mask "
                         "(build_dataset.py --min-cc-px; 0 = off)")
@@ -161,9 +164,11 @@ def main(argv=None):
         qc = TileQC(args.white_threshold, args.white_ratio_limit, args.blurry_threshold)
     raw_rgb = normalizer is not None or qc is not None
     cell_rows, shape_rows = [], []
-    if args.min_cc_px > 0 or args.cell_stats or args.cell_shapes:
+    post = args.morph_close_k > 0 or args.min_cc_px > 0 or args.cell_stats or args.cell_shapes
+    if post:
         import torch
 
+        from adipose_amd import morphology
         from adipose_amd.components import (CELL_SHAPES_HEADER, CELL_STATS_HEADER, cell_shapes, cell_shapes_row,
                                             cell_statistics, cell_stats_row, remove_small_components,
                                             stats_from_shapes)
@@ -211,10 +216,13 @@ def main(argv=None):
                 cell_rows.append(cell_stats_row(img_path.name))
             if args.cell_shapes:
                 shape_rows.append(cell_shapes_row(img_path.name))
-        elif args.min_cc_px > 0 or args.cell_stats or args.cell_shapes:
+        elif post:   # threshold -> close -> small components -> statistics, as the reference builds its masks
             mask_dev = torch.from_numpy(binary).cuda()
+            if args.morph_close_k > 0:
+                mask_dev = morphology.close(mask_dev, args.morph_close_k)
             if args.min_cc_px > 0:
                 mask_dev = remove_small_components(mask_dev, args.min_cc_px)
+            if args.morph_close_k > 0 or args.min_cc_px > 0:
                 binary = mask_dev.cpu().numpy()
             if args.cell_shapes:   # its dict holds the statistics too: with both flags the mask is labelled once
                 shapes = cell_shapes(mask_dev, args.cell_min_area, 0.5)

@@ -49,7 +49,8 @@ extern "C" {
                               v18: adp_conv_io.act_outA;
                               v19: adp_conv_desc.CA_real / CB_real / Nout_real (zero-weight hints);
                               v20: adp_wgrad_release / adp_wgrad_arena_chunks (deferral arenas per (device, stream)), adp_get_option;
-                              v21: adp_timing_filter */
+                              v21: adp_timing_filter; added under v21 (new exports only, nothing changed):
+                              adp_morph_pack / adp_morph_bits / adp_morph_unpack */
 
 typedef void* adp_stream_t; /* hipStream_t */
 
@@ -488,6 +489,35 @@ int adp_cc_relabel(int N, int H, int W, const int* labels, int* dense, adp_strea
  * NULL pointer (shape may be NULL only with max_rows = 0, which does nothing), max_rows < 0, a shape the other calls
  * refuse, or H*W*(max(H, W) - 1)^2 >= 2^63 (the moment sums are int64) */
 int adp_cc_shape(int N, int H, int W, const int* labels, int max_rows, long long* shape, adp_stream_t s);
+
+/* ---- binary mask morphology on bit-packed planes (morph_close, Segmentation/build_dataset.py:1190 and
+ *      build_test_dataset.py:596, flag --morph-close-k: cv2.morphologyEx(MORPH_CLOSE, getStructuringElement(
+ *      MORPH_ELLIPSE, (k, k))), the step before remove_small_components). A plane is (N, H, WW) 64-bit words,
+ *      WW = ceil(W / 64); bit b of word w of a row is pixel x = 64 w + b; the bits past W in a row's last word are 0 and
+ *      every call that writes a plane keeps them 0. All stream-ordered, none synchronises; exact and independent of N,
+ *      the grid and the run. N = 0 returns 0 without a launch ------------------------------------------------------ */
+#define ADP_MORPH_DILATE 0
+#define ADP_MORPH_ERODE 1
+#define ADP_MORPH_KMAX 63
+/* words a block of adp_morph_bits produces (tests place their shapes around it) */
+#define ADP_MORPH_TILE_ROWS 32
+#define ADP_MORPH_TILE_WORDS 8
+/* bits = the packed foreground of src (N, H, W) of src_dtype (ADP_CC_SRC_U8: byte != 0; ADP_CC_SRC_F32: value > thr) */
+int adp_morph_pack(int N, int H, int W, const void* src, int src_dtype, float thr, unsigned long long* bits,
+                   adp_stream_t s);
+/* dst = dilation (ADP_MORPH_DILATE) or erosion (ADP_MORPH_ERODE) of src by the footprint of ksize rows of column extents
+ * [row_lo[a], row_hi[a]) (HOST arrays, as adp_boundary_refine's), anchor ksize / 2 both ways:
+ *   dilate(M)(y, x) = OR  over row_lo[a] <= b < row_hi[a] of M(y + a - ksize/2, x + b - ksize/2)
+ *   erode(M)(y, x)  = AND over the same offsets (not the reflected ones)
+ * positions outside the image take no part in either (OpenCV's default morphology border: an all-ones mask erodes to
+ * all ones). 1 <= ksize <= ADP_MORPH_KMAX; src must not overlap dst. Fails (message, nothing launched) on a NULL
+ * pointer, N < 0, H or W < 1, a ksize out of range, a row with row_lo < 0, row_hi > ksize or row_lo > row_hi, an unknown
+ * op, or overlapping planes */
+int adp_morph_bits(int N, int H, int W, const unsigned long long* src, unsigned long long* dst, int ksize,
+                   const int* row_lo, const int* row_hi, int op, adp_stream_t s);
+/* the plane as 0 / 1 uint8 and / or 0.0 / 1.0 f32, (N, H, W) each (either may be NULL, not both) */
+int adp_morph_unpack(int N, int H, int W, const unsigned long long* bits, uint8_t* out_u8, float* out_f32,
+                     adp_stream_t s);
 
 /* ---- optimizer (Keras Adam / AdamW, :800-806) --------------------------------------------- */
 int adp_adam(size_t n, float* param, const float* grad, float* m, float* v, float lr, float beta1,
