@@ -128,6 +128,11 @@ _SIGS = {
     "adp_morph_pack": [_I, _I, _I, _P, _I, _F, _P, _P],
     "adp_morph_bits": [_I, _I, _I, _P, _P, _I, C.POINTER(C.c_int), C.POINTER(C.c_int), _I, _P],
     "adp_morph_unpack": [_I, _I, _I, _P, _P, _P, _P],
+    "adp_clahe_hist": [_I, _I, _I, _P, _I, _I, _I, _P, _P],
+    "adp_clahe_lut": [_I, _I, _I, _I, C.c_double, _P, _P, _P],
+    "adp_clahe_apply": [_I, _I, _I, _P, _I, _I, _I, _P, _P, _I, _P],
+    "adp_gray_stats": [_I, _I, _I, _P, _I, _P, _P],
+    "adp_u8_stretch": [_I, _S, _P, _P, C.c_double, C.c_double, _I, _P, _P],
     "adp_create": [_P, _I, _P],
     "adp_destroy": [_P],
     "adp_param_size": [_P, C.c_char_p, _I, C.POINTER(C.c_size_t)],

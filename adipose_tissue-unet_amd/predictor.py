@@ -25,6 +25,12 @@ Tile quality control at inference (quality.py; the reference's classify_tiles_ba
 network): a predictor with `tile_filter` set (a quality.TileQC) classifies raw uint8 RGB tiles / windows on the device
 and skips the forward for those in `skip_classes` (default: `empty`), whose probability map is all zero. Opt-in: with
 tile_filter=None every path runs as before.
+
+Contrast enhancement at inference (contrast.py; preprocess_small_MS_SIMs.py --enhance-contrast applies CLAHE to the
+whole image before it is tiled): a predictor with `contrast` set (a contrast.Clahe) passes every tile's gray plane
+through CLAHE on the device right before the input is prepared, after stain normalisation and gray conversion; the
+sliding window enhances a gray image once, as the reference does, and predicts its windows without per-tile
+enhancement. 1-channel networks only. Opt-in: with contrast=None every path runs as before.
 """
 from __future__ import annotations
 
@@ -71,13 +77,14 @@ def _pil_gray(rgb):
 class HipUnetPredictor:
     """GPU predictor: predict_single(image, mean, std) -> (S,S) float32 probabilities (main_out)."""
 
-    def __init__(self, net, max_batch=8, stain_normalizer=None, tile_filter=None, skip_classes=("empty",)):
+    def __init__(self, net, max_batch=8, stain_normalizer=None, tile_filter=None, skip_classes=("empty",), contrast=None):
         self.net = net
         self.device = net.device
         self.max_batch = max_batch
         self.stain_normalizer = stain_normalizer   # stain.ReinhardStainNormalizer: uint8 RGB tiles are accepted
         self.tile_filter = tile_filter             # quality.TileQC: uint8 RGB tiles are classified, some skipped
         self.skip_classes = tuple(skip_classes)
+        self.contrast = contrast                   # contrast.Clahe: every tile's gray plane is enhanced on the device
         self.last_tile_classes = None              # classes of the last predict_views call's tiles, in input order
         self._packed_step = None
 
@@ -90,12 +97,17 @@ class HipUnetPredictor:
         outs = net.forward(batch, train=False, pack=True)
         return outs["main_out"]
 
-    def predict_views(self, images, mean, std, views, classify=True):
+    def predict_views(self, images, mean, std, views, classify=True, enhance=True):
         """images: list/tensor of (S,S) tiles (device or host, may be strided windows); returns
         (len(images), S, S) device tensor of TTA-merged probabilities. With a stain normaliser or a tile filter the
         tiles may be raw (S, S, 3) uint8 RGB. With a tile filter (and classify=True; the sliding window, which has
         classified its windows already, passes False) uint8 RGB tiles are classified in one call: those in
-        skip_classes get an all-zero map and take no part in any forward; last_tile_classes holds the classes."""
+        skip_classes get an all-zero map and take no part in any forward; last_tile_classes holds the classes. With
+        `contrast` set (and enhance=True; the sliding window, which has enhanced its gray image as a whole, passes False)
+        every tile's gray plane goes through CLAHE before the input is prepared."""
+        contrast = self.contrast if enhance else None
+        if contrast is not None and getattr(self.net, "in_ch", 1) != 1:
+            raise ValueError("contrast enhancement works on the gray plane of a 1-channel network")
         n_img = len(images)
         nv = len(views)
         plain = self.stain_normalizer is None and self.tile_filter is None
@@ -122,6 +134,8 @@ class HipUnetPredictor:
                          .to(self.device).float() if rgb3 else _pil_gray(t) for t in chunk]
             B = len(chunk) * nv
             a = self.net.acts(B)
+            if contrast is not None:   # one batched CLAHE of the chunk's gray planes (f32 in, f32 out, the same integers)
+                chunk = contrast(torch.stack([_to_dev(img, self.device) for img in chunk]))
             for t, img in enumerate(chunk):
                 src = _to_dev(img, self.device)[None]
                 for k, v in enumerate(views):
@@ -156,8 +170,9 @@ class AdiposeUNet:
     predict_single / predict). ``dtype='f32'`` reproduces the reference's fp32 numerics."""
 
     def __init__(self, tile_size=1024, dtype="f32", device="cuda", max_batch=8, stain_normalizer=None,
-                 tile_filter=None, skip_classes=("empty",)):
+                 tile_filter=None, skip_classes=("empty",), contrast=None):
         self.net = None
+        self.contrast = contrast
         self.stain_normalizer = stain_normalizer
         self.tile_filter = tile_filter
         self.skip_classes = tuple(skip_classes)
@@ -176,7 +191,7 @@ class AdiposeUNet:
         self.net = AdiposeV3Net(1, self.tile_size, dtype=self.dtype, device=self.device, init_nb=init_nb, cpad=cpad,
                                 dropout_rate=dropout_rate, deep_supervision=use_deep_supervision)
         self._pred = HipUnetPredictor(self.net, self.max_batch, self.stain_normalizer, self.tile_filter,
-                                      self.skip_classes)
+                                      self.skip_classes, self.contrast)
         return self.net
 
     def load_weights(self, weights_path: str):
@@ -187,6 +202,7 @@ class AdiposeUNet:
     def _sync(self):
         p = self._pred
         p.stain_normalizer, p.tile_filter, p.skip_classes = self.stain_normalizer, self.tile_filter, tuple(self.skip_classes)
+        p.contrast = self.contrast
         return p
 
     @property
@@ -196,8 +212,8 @@ class AdiposeUNet:
     def predict_single(self, image, mean, std):
         return self._sync().predict_single(image, mean, std)
 
-    def predict_views(self, images, mean, std, views, classify=True):
-        return self._sync().predict_views(images, mean, std, views, classify)
+    def predict_views(self, images, mean, std, views, classify=True, enhance=True):
+        return self._sync().predict_views(images, mean, std, views, classify, enhance)
 
     def predict(self, image, mean, std, use_tta=False, tta_mode="basic"):
         """full_evaluation_enhanced.py:1323-1353 -> (pred, timing_info)"""
@@ -438,6 +454,13 @@ class SlidingWindowInference:
             img = (torch.from_numpy(np.ascontiguousarray(image)) if isinstance(image, np.ndarray) else image).to(dev)
         else:
             img = _to_dev(image, dev)
+        kw = {}
+        contrast = getattr(model, "contrast", None)
+        if contrast is not None and img.dim() == 2:
+            # a gray image is enhanced once as a whole (preprocess_small_MS_SIMs.py enhances before it tiles); its
+            # windows are then predicted without per-tile enhancement. RGB windows are enhanced inside predict_views
+            img = contrast(img)
+            kw["enhance"] = False
         h, w = img.shape[:2]
         T = self.tile_size
         positions = self.extract_tile_positions((h, w))
@@ -456,11 +479,11 @@ class SlidingWindowInference:
         # tile quality control: this rank's windows are classified in place with one launch; a skipped window enters
         # the canvas as a zero tile with its blending weight (the network is taken to have said "background")
         self.last_tile_classes = None
-        skip, kw, zero = [False] * len(mine), {}, None
+        skip, zero = [False] * len(mine), None
         if tile_filter is not None and _is_rgb_u8(img) and mine:
             self.last_tile_classes = tile_filter.classify_windows(img, mine, T)
             skip = [c in tuple(getattr(model, "skip_classes", ("empty",))) for c in self.last_tile_classes]
-            kw = {"classify": False}
+            kw["classify"] = False
             if any(skip):
                 zero = torch.zeros((T, T), dtype=torch.float32, device=dev)
         pending = []   # windows in order; forwarded (and all of them blended, in order) once `per` are to be predicted

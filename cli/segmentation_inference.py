@@ -16,6 +16,9 @@ classify_tiles_batch, build_dataset.py:1253-1284; --white-threshold, --white-rat
 defaults). Empty tiles (with --skip-blurry also blurry ones) get an all-zero mask without a forward; `tile_qc.csv` in
 the output directory lists every tile's measurements and class. The files of the other tiles are what they are without
 the flag.
+--enhance-contrast: every tile's gray plane goes through CLAHE on the GPU before the network (contrast.py;
+preprocess_small_MS_SIMs.py's flag, with its --clahe-tile-size 16 and --clahe-clip-limit 3.0). The run's header names
+the enhancement only when it is set.
 """
 import argparse
 import json
@@ -88,6 +91,12 @@ def build_parser():
     q.add_argument("--blurry-threshold", type=float, default=7.5, help="blurry: variance of the Laplacian below this")
     q.add_argument("--skip-blurry", action="store_true", default=False,
                    help="skip blurry tiles too (default: only empty ones, as the reference keeps blurry tiles)")
+    e = p.add_argument_group("contrast enhancement (on the device)")
+    e.add_argument("--enhance-contrast", action="store_true", default=False,
+                   help="CLAHE on every tile's gray plane before the network (preprocess_small_MS_SIMs.py "
+                        "--enhance-contrast)")
+    e.add_argument("--clahe-tile-size", type=int, default=16, help="CLAHE grid: this many tiles both ways (1..64)")
+    e.add_argument("--clahe-clip-limit", type=float, default=3.0, help="CLAHE clip limit")
     c = p.add_argument_group("connected components (on the device)")
     c.add_argument("--morph-close-k", type=int, default=0, choices=range(0, 64), metavar="K",
                    help="close the binarised mask with a K x K ellipse before anything else is done with it "
@@ -149,7 +158,19 @@ def main(argv=None):
         except (FileNotFoundError, ValueError) as e:
             print(f"❌ {e}")
             return 1
-    model = AdiposeUNet(tile_size=args.tile, dtype=args.dtype, max_batch=args.batch, stain_normalizer=normalizer)
+    contrast = None
+    if args.enhance_contrast:
+        from adipose_amd.contrast import Clahe, clahe_geometry
+        try:
+            contrast = Clahe(args.clahe_clip_limit, args.clahe_tile_size)
+            clahe_geometry(args.tile, args.tile, contrast.tile_grid)
+        except ValueError as e:
+            print(f"❌ {e}")
+            return 1
+        print(f"✓ Contrast enhancement: CLAHE clip limit {contrast.clip_limit:g}, "
+              f"{contrast.tile_size} x {contrast.tile_size} tiles")
+    model = AdiposeUNet(tile_size=args.tile, dtype=args.dtype, max_batch=args.batch, stain_normalizer=normalizer,
+                        contrast=contrast)
     model.build_model()
     model.load_weights(weights_file)
     mean, std = load_normalization_stats(checkpoint_dir)

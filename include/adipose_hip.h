@@ -50,7 +50,8 @@ extern "C" {
                               v19: adp_conv_desc.CA_real / CB_real / Nout_real (zero-weight hints);
                               v20: adp_wgrad_release / adp_wgrad_arena_chunks (deferral arenas per (device, stream)), adp_get_option;
                               v21: adp_timing_filter; added under v21 (new exports only, nothing changed):
-                              adp_morph_pack / adp_morph_bits / adp_morph_unpack */
+                              adp_morph_pack / adp_morph_bits / adp_morph_unpack;
+                              adp_clahe_hist / adp_clahe_lut / adp_clahe_apply, adp_gray_stats, adp_u8_stretch */
 
 typedef void* adp_stream_t; /* hipStream_t */
 
@@ -518,6 +519,40 @@ int adp_morph_bits(int N, int H, int W, const unsigned long long* src, unsigned 
 /* the plane as 0 / 1 uint8 and / or 0.0 / 1.0 f32, (N, H, W) each (either may be NULL, not both) */
 int adp_morph_unpack(int N, int H, int W, const unsigned long long* bits, uint8_t* out_u8, float* out_f32,
                      adp_stream_t s);
+
+/* ---- contrast-limited adaptive histogram equalisation of 8-bit gray planes (cv2.createCLAHE(clip_limit, (tx, ty))
+ *      .apply: pre-post-processing_tools/preprocess_small_MS_SIMs.py:393-431 --enhance-contrast,
+ *      large_wsi_to_small_wsi_MS.py:202-210 enhance_clahe, adaptive_clahe_function.py). The definition (OpenCV 4's
+ *      clahe.cpp for 8-bit input, restated) is in contrast.py. A plane is (N, H, W) uint8, or float32 (src_f32 != 0)
+ *      rounded to nearest and clamped to 0 .. 255 on load. The grid has ty rows of tx tiles, each 1 .. ADP_CLAHE_MAX_GRID;
+ *      the image is extended by reflect-101 at the bottom and right to (He, We) -- both axes by a full ty - H % ty /
+ *      tx - W % tx unless both divide evenly -- by index arithmetic; tiles are th x tw = He / ty x We / tx. All
+ *      stream-ordered, none synchronises; integer up to the tables and single float32 operations after, so exact and
+ *      independent of N, the grid and the run. Every call fails (message, nothing launched, outputs untouched) on a
+ *      NULL pointer, N < 1, a grid outside 1 .. 64, or an extension beyond dim - 1 ------------------------------------ */
+#define ADP_CLAHE_MAX_GRID 64
+/* rows x columns of a tile that one block of adp_clahe_hist counts (tests place their shapes around them) */
+#define ADP_CLAHE_SLAB_ROWS 64
+#define ADP_CLAHE_SLAB_COLS 1024
+/* hist (N, ty, tx, 256) uint32: the histograms of the extended image's tiles; the call zeroes it. With ty = tx = 1
+ * the global histogram adp_u8_stretch reads */
+int adp_clahe_hist(int N, int H, int W, const void* src, int src_f32, int ty, int tx, uint32_t* hist, adp_stream_t s);
+/* lut (N, ty, tx, 256) uint8 from hist of tiles of `area` pixels: clip = max(int(clip_limit * area / 256), 1) (none
+ * if clip_limit <= 0), the excess redistributed as OpenCV does, lut[i] = saturate(rint(float(cumsum[i]) * (255f / area))) */
+int adp_clahe_lut(int N, int ty, int tx, int area, double clip_limit, const uint32_t* hist, uint8_t* lut, adp_stream_t s);
+/* dst (N, H, W) = the bilinear blend of the four neighbouring tiles' tables at src's value; uint8, or float32
+ * (dst_f32 != 0) holding the same integers. lut must be 16-byte aligned */
+int adp_clahe_apply(int N, int H, int W, const void* src, int src_f32, int ty, int tx, const uint8_t* lut, void* dst,
+                    int dst_f32, adp_stream_t s);
+/* sums (N, 5) int64 {sum g, sum g^2, sum lap, sum lap^2, H * W}; lap = g(y-1,x) + g(y+1,x) + g(y,x-1) + g(y,x+1) -
+ * 4 g(y,x) with reflect-101 borders (cv2.Laplacian, ksize 1). H and W at least 2. The call zeroes sums */
+int adp_gray_stats(int N, int H, int W, const void* src, int src_f32, long long* sums, adp_stream_t s);
+/* dst (N, n_px) f32 = clip((src - lo) / den, 0, 1) per image; lo / hi are the image's p_low / p_high percentiles
+ * (numpy's "linear" method, float64, found on the device from hist (N, 256), the image's histogram as adp_clahe_hist
+ * writes it on a 1 x 1 grid); den = (hi - lo) + 1e-3 (mode 0) or max(hi - lo, 1e-3) (mode 1); float64 arithmetic,
+ * rounded to float32 once */
+int adp_u8_stretch(int N, size_t n_px, const uint8_t* src, const uint32_t* hist, double p_low, double p_high, int mode,
+                   float* dst, adp_stream_t s);
 
 /* ---- optimizer (Keras Adam / AdamW, :800-806) --------------------------------------------- */
 int adp_adam(size_t n, float* param, const float* grad, float* m, float* v, float lr, float beta1,
