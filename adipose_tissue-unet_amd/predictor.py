@@ -31,6 +31,13 @@ whole image before it is tiled): a predictor with `contrast` set (a contrast.Cla
 through CLAHE on the device right before the input is prepared, after stain normalisation and gray conversion; the
 sliding window enhances a gray image once, as the reference does, and predicts its windows without per-tile
 enhancement. 1-channel networks only. Opt-in: with contrast=None every path runs as before.
+
+Background correction at inference (illumination.py; preprocess_ecm_image removes banding and corrects illumination by
+gray-scale morphology before it enhances contrast): a predictor with `illumination` set (an
+illumination.IlluminationCorrection) passes every tile's gray plane through it on the device, after stain
+normalisation and gray conversion and before `contrast`. The sliding window corrects a gray image once as a whole and
+predicts its windows without per-tile correction; per tile, a correction differs from the whole image's within a
+footprint radius of the tile's edges. 1-channel networks only. Opt-in: with illumination=None every path runs as before.
 """
 from __future__ import annotations
 
@@ -77,7 +84,8 @@ def _pil_gray(rgb):
 class HipUnetPredictor:
     """GPU predictor: predict_single(image, mean, std) -> (S,S) float32 probabilities (main_out)."""
 
-    def __init__(self, net, max_batch=8, stain_normalizer=None, tile_filter=None, skip_classes=("empty",), contrast=None):
+    def __init__(self, net, max_batch=8, stain_normalizer=None, tile_filter=None, skip_classes=("empty",), contrast=None,
+                 illumination=None):
         self.net = net
         self.device = net.device
         self.max_batch = max_batch
@@ -85,6 +93,7 @@ class HipUnetPredictor:
         self.tile_filter = tile_filter             # quality.TileQC: uint8 RGB tiles are classified, some skipped
         self.skip_classes = tuple(skip_classes)
         self.contrast = contrast                   # contrast.Clahe: every tile's gray plane is enhanced on the device
+        self.illumination = illumination           # illumination.IlluminationCorrection: applied before `contrast`
         self.last_tile_classes = None              # classes of the last predict_views call's tiles, in input order
         self._packed_step = None
 
@@ -104,10 +113,14 @@ class HipUnetPredictor:
         classified its windows already, passes False) uint8 RGB tiles are classified in one call: those in
         skip_classes get an all-zero map and take no part in any forward; last_tile_classes holds the classes. With
         `contrast` set (and enhance=True; the sliding window, which has enhanced its gray image as a whole, passes False)
-        every tile's gray plane goes through CLAHE before the input is prepared."""
+        every tile's gray plane goes through CLAHE before the input is prepared; with `illumination` set (and
+        enhance=True) through the background correction before that."""
         contrast = self.contrast if enhance else None
         if contrast is not None and getattr(self.net, "in_ch", 1) != 1:
             raise ValueError("contrast enhancement works on the gray plane of a 1-channel network")
+        illumination = self.illumination if enhance else None
+        if illumination is not None and getattr(self.net, "in_ch", 1) != 1:
+            raise ValueError("background correction works on the gray plane of a 1-channel network")
         n_img = len(images)
         nv = len(views)
         plain = self.stain_normalizer is None and self.tile_filter is None
@@ -134,6 +147,8 @@ class HipUnetPredictor:
                          .to(self.device).float() if rgb3 else _pil_gray(t) for t in chunk]
             B = len(chunk) * nv
             a = self.net.acts(B)
+            if illumination is not None:   # one batched correction of the chunk's gray planes (f32 in, f32 out)
+                chunk = illumination(torch.stack([_to_dev(img, self.device) for img in chunk]))
             if contrast is not None:   # one batched CLAHE of the chunk's gray planes (f32 in, f32 out, the same integers)
                 chunk = contrast(torch.stack([_to_dev(img, self.device) for img in chunk]))
             for t, img in enumerate(chunk):
@@ -170,9 +185,10 @@ class AdiposeUNet:
     predict_single / predict). ``dtype='f32'`` reproduces the reference's fp32 numerics."""
 
     def __init__(self, tile_size=1024, dtype="f32", device="cuda", max_batch=8, stain_normalizer=None,
-                 tile_filter=None, skip_classes=("empty",), contrast=None):
+                 tile_filter=None, skip_classes=("empty",), contrast=None, illumination=None):
         self.net = None
         self.contrast = contrast
+        self.illumination = illumination
         self.stain_normalizer = stain_normalizer
         self.tile_filter = tile_filter
         self.skip_classes = tuple(skip_classes)
@@ -191,7 +207,7 @@ class AdiposeUNet:
         self.net = AdiposeV3Net(1, self.tile_size, dtype=self.dtype, device=self.device, init_nb=init_nb, cpad=cpad,
                                 dropout_rate=dropout_rate, deep_supervision=use_deep_supervision)
         self._pred = HipUnetPredictor(self.net, self.max_batch, self.stain_normalizer, self.tile_filter,
-                                      self.skip_classes, self.contrast)
+                                      self.skip_classes, self.contrast, self.illumination)
         return self.net
 
     def load_weights(self, weights_path: str):
@@ -203,6 +219,7 @@ class AdiposeUNet:
         p = self._pred
         p.stain_normalizer, p.tile_filter, p.skip_classes = self.stain_normalizer, self.tile_filter, tuple(self.skip_classes)
         p.contrast = self.contrast
+        p.illumination = self.illumination
         return p
 
     @property
@@ -456,6 +473,11 @@ class SlidingWindowInference:
             img = _to_dev(image, dev)
         kw = {}
         contrast = getattr(model, "contrast", None)
+        illumination = getattr(model, "illumination", None)
+        if illumination is not None and img.dim() == 2:
+            # a gray image is corrected once as a whole, before its contrast is enhanced (preprocess_ecm_image's order)
+            img = illumination(img)
+            kw["enhance"] = False
         if contrast is not None and img.dim() == 2:
             # a gray image is enhanced once as a whole (preprocess_small_MS_SIMs.py enhances before it tiles); its
             # windows are then predicted without per-tile enhancement. RGB windows are enhanced inside predict_views

@@ -19,6 +19,11 @@ the flag.
 --enhance-contrast: every tile's gray plane goes through CLAHE on the GPU before the network (contrast.py;
 preprocess_small_MS_SIMs.py's flag, with its --clahe-tile-size 16 and --clahe-clip-limit 3.0). The run's header names
 the enhancement only when it is set.
+--illumination-method rolling-ball | tophat (--rolling-ball-radius 100, --tophat-kernel 301) and --banding-method
+morphological (--morph-width 1, --morph-height 512): preprocess_small_MS_SIMs.py's background corrections by gray-scale
+morphology (illumination.py), on every tile's gray plane on the GPU, banding removal first, before --enhance-contrast.
+Applied per tile, a correction differs from that of the whole slide within a footprint radius of the tile's edges, and
+its background mean is the tile's own. Sizes are checked against the kernel's limit before a model is loaded.
 """
 import argparse
 import json
@@ -97,6 +102,16 @@ def build_parser():
                         "--enhance-contrast)")
     e.add_argument("--clahe-tile-size", type=int, default=16, help="CLAHE grid: this many tiles both ways (1..64)")
     e.add_argument("--clahe-clip-limit", type=float, default=3.0, help="CLAHE clip limit")
+    b = p.add_argument_group("background correction by gray-scale morphology (on the device)")
+    b.add_argument("--illumination-method", type=str, default="none", choices=["none", "rolling-ball", "tophat"],
+                   help="illumination correction of every tile's gray plane (preprocess_small_MS_SIMs.py's methods by "
+                        "morphology)")
+    b.add_argument("--rolling-ball-radius", type=int, default=100, help="radius of the rolling ball's disc (0..256)")
+    b.add_argument("--tophat-kernel", type=int, default=301, help="size of the top-hat's ellipse (even: the next odd; 1..513)")
+    b.add_argument("--banding-method", type=str, default="none", choices=["none", "morphological"],
+                   help="banding removal before the illumination method")
+    b.add_argument("--morph-width", type=int, default=1, help="width of the banding opening's rectangle (1..513)")
+    b.add_argument("--morph-height", type=int, default=512, help="height of the banding opening's rectangle (1..513)")
     c = p.add_argument_group("connected components (on the device)")
     c.add_argument("--morph-close-k", type=int, default=0, choices=range(0, 64), metavar="K",
                    help="close the binarised mask with a K x K ellipse before anything else is done with it "
@@ -114,8 +129,26 @@ def build_parser():
     return p
 
 
+def build_illumination(args):
+    """The IlluminationCorrection the flags ask for, or None; ValueError on a size the kernel does not take. Needs no
+    device."""
+    if args.illumination_method == "none" and args.banding_method == "none":
+        return None
+    import _adipose_pkg  # noqa: F401
+    from adipose_amd.illumination import IlluminationCorrection
+    return IlluminationCorrection(
+        banding=(args.morph_width, args.morph_height) if args.banding_method == "morphological" else None,
+        method=None if args.illumination_method == "none" else args.illumination_method,
+        radius=args.rolling_ball_radius, kernel_size=args.tophat_kernel)
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    try:
+        illumination = build_illumination(args)
+    except ValueError as e:
+        print(f"❌ {e}")
+        return 1
     images_dir, output_dir = Path(args.images_dir), Path(args.output_dir)
     if not images_dir.exists():
         print(f"❌ Error: Images directory not found: {images_dir}")
@@ -169,8 +202,10 @@ def main(argv=None):
             return 1
         print(f"✓ Contrast enhancement: CLAHE clip limit {contrast.clip_limit:g}, "
               f"{contrast.tile_size} x {contrast.tile_size} tiles")
+    if illumination is not None:
+        print(f"✓ Background correction: {illumination}")
     model = AdiposeUNet(tile_size=args.tile, dtype=args.dtype, max_batch=args.batch, stain_normalizer=normalizer,
-                        contrast=contrast)
+                        contrast=contrast, illumination=illumination)
     model.build_model()
     model.load_weights(weights_file)
     mean, std = load_normalization_stats(checkpoint_dir)

@@ -51,7 +51,8 @@ extern "C" {
                               v20: adp_wgrad_release / adp_wgrad_arena_chunks (deferral arenas per (device, stream)), adp_get_option;
                               v21: adp_timing_filter; added under v21 (new exports only, nothing changed):
                               adp_morph_pack / adp_morph_bits / adp_morph_unpack;
-                              adp_clahe_hist / adp_clahe_lut / adp_clahe_apply, adp_gray_stats, adp_u8_stretch */
+                              adp_clahe_hist / adp_clahe_lut / adp_clahe_apply, adp_gray_stats, adp_u8_stretch;
+                              adp_gray_morph / adp_gray_bgsum / adp_illum_finish */
 
 typedef void* adp_stream_t; /* hipStream_t */
 
@@ -553,6 +554,40 @@ int adp_gray_stats(int N, int H, int W, const void* src, int src_f32, long long*
  * rounded to float32 once */
 int adp_u8_stretch(int N, size_t n_px, const uint8_t* src, const uint32_t* hist, double p_low, double p_high, int mode,
                    float* dst, adp_stream_t s);
+
+/* ---- gray-scale (flat) morphology of 8-bit planes and the background corrections built on it
+ *      (pre-post-processing_tools/preprocess_small_MS_SIMs.py:217-246 remove_banding_morphological, 293-326
+ *      correct_illumination_rolling_ball, 357-390 correct_illumination_tophat). The definitions are in illumination.py.
+ *      A plane is (N, H, W) uint8, or float32 (the _f32 flag != 0) rounded to nearest and clamped to 0 .. 255 on load.
+ *      All stream-ordered, none synchronises; integers and single exact float32 operations, so exact and independent of
+ *      N, the grid and the run. N = 0 returns 0 without a launch. Every call fails (message, nothing launched, outputs
+ *      untouched) on a NULL pointer, N < 0, H or W < 1, or an output that overlaps an input -------------------------- */
+#define ADP_GMORPH_ERODE 0
+#define ADP_GMORPH_DILATE 1
+#define ADP_GMORPH_KMAX 513 /* rows and box width of a footprint: the reference's 512 x 1 line, 301 ellipse, 401 disc */
+/* pixels a block of adp_gray_morph produces (tests place their shapes around them) */
+#define ADP_GMORPH_TILE_ROWS 64
+#define ADP_GMORPH_TILE_COLS 256
+/* dst (N, H, W) uint8 = erosion (ADP_GMORPH_ERODE) or dilation (ADP_GMORPH_DILATE) of src by the footprint of kh rows of
+ * column extents [row_lo[a], row_hi[a]) (HOST arrays) in a box kw wide, anchor (kh / 2, kw / 2):
+ *   erode(M)(y, x)  = min over rows a, row_lo[a] <= b < row_hi[a], of M(y + a - kh/2, x + b - kw/2)
+ *   dilate(M)(y, x) = max over the same offsets (not the reflected ones)
+ * positions outside the image take no part (OpenCV's default morphology border); an empty footprint erodes to 255 and
+ * dilates to 0; a footprint may be larger than the image. 1 <= kh, kw <= ADP_GMORPH_KMAX. Also fails on a size out of
+ * range, a row with row_lo < 0, row_hi > kw or row_lo > row_hi, or an unknown op */
+int adp_gray_morph(int N, int H, int W, const void* src, int src_f32, uint8_t* dst, int kh, int kw, const int* row_lo,
+                   const int* row_hi, int op, adp_stream_t s);
+/* sums (N) int64 = the sum of every image of the uint8 plane src (integer atomics: exact in any order). H * W < 2^31,
+ * N <= 65535. The call zeroes sums */
+int adp_gray_bgsum(int N, int H, int W, const uint8_t* src, long long* sums, adp_stream_t s);
+#define ADP_ILLUM_SUBTRACT_MEAN 0 /* dst = trunc(clip(float(v - b) + mean32, 0, 255)), mean32 = float(double(sums[n]) / double(H * W)) */
+#define ADP_ILLUM_TOPHAT_HALF 1   /* dst = trunc(clip(float(v) + float(max(v - b, 0)) * 0.5f, 0, 255)); b = open(v) */
+#define ADP_ILLUM_DIFF 2          /* dst = max(v - b, 0): the white top-hat (v, open(v)) and the black one (close(v), v) */
+/* the element-wise end of the corrections: v (N, H, W) uint8 or float32, b (N, H, W) uint8 (the background, or the
+ * opening), sums (N) int64 as adp_gray_bgsum writes it (read on the device; may be NULL for the other two modes),
+ * dst uint8 or float32 (dst_f32 != 0) holding the same integers. Also fails on an unknown mode or N > 65535 */
+int adp_illum_finish(int N, int H, int W, const void* v, int v_f32, const uint8_t* b, const long long* sums, int mode,
+                     void* dst, int dst_f32, adp_stream_t s);
 
 /* ---- optimizer (Keras Adam / AdamW, :800-806) --------------------------------------------- */
 int adp_adam(size_t n, float* param, const float* grad, float* m, float* v, float lr, float beta1,
