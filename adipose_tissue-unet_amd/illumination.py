@@ -458,14 +458,22 @@ class IlluminationCorrection:
                 raise ValueError("kernel_size must be at least 1")
             ellipse_rows(_odd(self.kernel_size))
 
-    def __call__(self, img):
+    def remove_banding(self, img):
+        """The banding step alone (the reference normalises between it and the illumination step: normalization.py)."""
         if self.banding is not None:
             img = remove_banding(img, self.banding[0], self.banding[1])
+        return img
+
+    def correct(self, img):
+        """The illumination step alone."""
         if self.method == "rolling-ball":
             img = correct_illumination_rolling_ball(img, self.radius)
         elif self.method == "tophat":
             img = correct_illumination_tophat(img, self.kernel_size)
         return img
+
+    def __call__(self, img):
+        return self.correct(self.remove_banding(img))
 
     def __repr__(self):
         return (f"IlluminationCorrection(banding={self.banding}, method={self.method!r}, radius={self.radius}, "

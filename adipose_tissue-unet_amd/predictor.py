@@ -38,6 +38,13 @@ illumination.IlluminationCorrection) passes every tile's gray plane through it o
 normalisation and gray conversion and before `contrast`. The sliding window corrects a gray image once as a whole and
 predicts its windows without per-tile correction; per tile, a correction differs from the whole image's within a
 footprint radius of the tile's edges. 1-channel networks only. Opt-in: with illumination=None every path runs as before.
+
+Statistical normalisation at inference (normalization.py; preprocess_ecm_image's column de-banding and its z-score /
+percentile stretch): a predictor with `normalization` set (a normalization.GrayNormalization) runs the reference's order
+on every chunk of gray planes on the device: normalization.remove_banding, illumination.remove_banding,
+normalization.normalize, illumination.correct, contrast. The sliding window does the same once on the whole gray image
+and predicts its windows without per-tile steps; per tile the statistics are the tile's. 1-channel networks only.
+Opt-in: with normalization=None every path runs as before.
 """
 from __future__ import annotations
 
@@ -85,7 +92,7 @@ class HipUnetPredictor:
     """GPU predictor: predict_single(image, mean, std) -> (S,S) float32 probabilities (main_out)."""
 
     def __init__(self, net, max_batch=8, stain_normalizer=None, tile_filter=None, skip_classes=("empty",), contrast=None,
-                 illumination=None):
+                 illumination=None, normalization=None):
         self.net = net
         self.device = net.device
         self.max_batch = max_batch
@@ -94,6 +101,7 @@ class HipUnetPredictor:
         self.skip_classes = tuple(skip_classes)
         self.contrast = contrast                   # contrast.Clahe: every tile's gray plane is enhanced on the device
         self.illumination = illumination           # illumination.IlluminationCorrection: applied before `contrast`
+        self.normalization = normalization         # normalization.GrayNormalization: around the banding step (below)
         self.last_tile_classes = None              # classes of the last predict_views call's tiles, in input order
         self._packed_step = None
 
@@ -114,13 +122,18 @@ class HipUnetPredictor:
         skip_classes get an all-zero map and take no part in any forward; last_tile_classes holds the classes. With
         `contrast` set (and enhance=True; the sliding window, which has enhanced its gray image as a whole, passes False)
         every tile's gray plane goes through CLAHE before the input is prepared; with `illumination` set (and
-        enhance=True) through the background correction before that."""
+        enhance=True) through the background correction before that; with `normalization` set (and enhance=True) the
+        order is normalization.remove_banding, illumination.remove_banding, normalization.normalize,
+        illumination.correct, contrast."""
         contrast = self.contrast if enhance else None
         if contrast is not None and getattr(self.net, "in_ch", 1) != 1:
             raise ValueError("contrast enhancement works on the gray plane of a 1-channel network")
         illumination = self.illumination if enhance else None
         if illumination is not None and getattr(self.net, "in_ch", 1) != 1:
             raise ValueError("background correction works on the gray plane of a 1-channel network")
+        normalization = self.normalization if enhance else None
+        if normalization is not None and getattr(self.net, "in_ch", 1) != 1:
+            raise ValueError("gray normalisation works on the gray plane of a 1-channel network")
         n_img = len(images)
         nv = len(views)
         plain = self.stain_normalizer is None and self.tile_filter is None
@@ -147,7 +160,14 @@ class HipUnetPredictor:
                          .to(self.device).float() if rgb3 else _pil_gray(t) for t in chunk]
             B = len(chunk) * nv
             a = self.net.acts(B)
-            if illumination is not None:   # one batched correction of the chunk's gray planes (f32 in, f32 out)
+            if normalization is not None:   # the reference's order around the banding step, batched (f32 in, f32 out)
+                chunk = normalization.remove_banding(torch.stack([_to_dev(img, self.device) for img in chunk]))
+                if illumination is not None:
+                    chunk = illumination.remove_banding(chunk)
+                chunk = normalization.normalize(chunk)
+                if illumination is not None:
+                    chunk = illumination.correct(chunk)
+            elif illumination is not None:   # one batched correction of the chunk's gray planes (f32 in, f32 out)
                 chunk = illumination(torch.stack([_to_dev(img, self.device) for img in chunk]))
             if contrast is not None:   # one batched CLAHE of the chunk's gray planes (f32 in, f32 out, the same integers)
                 chunk = contrast(torch.stack([_to_dev(img, self.device) for img in chunk]))
@@ -185,10 +205,11 @@ class AdiposeUNet:
     predict_single / predict). ``dtype='f32'`` reproduces the reference's fp32 numerics."""
 
     def __init__(self, tile_size=1024, dtype="f32", device="cuda", max_batch=8, stain_normalizer=None,
-                 tile_filter=None, skip_classes=("empty",), contrast=None, illumination=None):
+                 tile_filter=None, skip_classes=("empty",), contrast=None, illumination=None, normalization=None):
         self.net = None
         self.contrast = contrast
         self.illumination = illumination
+        self.normalization = normalization
         self.stain_normalizer = stain_normalizer
         self.tile_filter = tile_filter
         self.skip_classes = tuple(skip_classes)
@@ -207,7 +228,7 @@ class AdiposeUNet:
         self.net = AdiposeV3Net(1, self.tile_size, dtype=self.dtype, device=self.device, init_nb=init_nb, cpad=cpad,
                                 dropout_rate=dropout_rate, deep_supervision=use_deep_supervision)
         self._pred = HipUnetPredictor(self.net, self.max_batch, self.stain_normalizer, self.tile_filter,
-                                      self.skip_classes, self.contrast, self.illumination)
+                                      self.skip_classes, self.contrast, self.illumination, self.normalization)
         return self.net
 
     def load_weights(self, weights_path: str):
@@ -220,6 +241,7 @@ class AdiposeUNet:
         p.stain_normalizer, p.tile_filter, p.skip_classes = self.stain_normalizer, self.tile_filter, tuple(self.skip_classes)
         p.contrast = self.contrast
         p.illumination = self.illumination
+        p.normalization = self.normalization
         return p
 
     @property
@@ -474,7 +496,17 @@ class SlidingWindowInference:
         kw = {}
         contrast = getattr(model, "contrast", None)
         illumination = getattr(model, "illumination", None)
-        if illumination is not None and img.dim() == 2:
+        normalization = getattr(model, "normalization", None)
+        if normalization is not None and img.dim() == 2:
+            # a gray image is normalised once as a whole, in preprocess_ecm_image's order around the banding step
+            img = normalization.remove_banding(img)
+            if illumination is not None:
+                img = illumination.remove_banding(img)
+            img = normalization.normalize(img)
+            if illumination is not None:
+                img = illumination.correct(img)
+            kw["enhance"] = False
+        elif illumination is not None and img.dim() == 2:
             # a gray image is corrected once as a whole, before its contrast is enhanced (preprocess_ecm_image's order)
             img = illumination(img)
             kw["enhance"] = False

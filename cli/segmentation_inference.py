@@ -24,6 +24,10 @@ morphological (--morph-width 1, --morph-height 512): preprocess_small_MS_SIMs.py
 morphology (illumination.py), on every tile's gray plane on the GPU, banding removal first, before --enhance-contrast.
 Applied per tile, a correction differs from that of the whole slide within a footprint radius of the tile's edges, and
 its background mean is the tile's own. Sizes are checked against the kernel's limit before a model is loaded.
+--banding-method column (--column-preserve-global) and --normalization-method percentile | zscore (--percentile-low 1,
+--percentile-high 99): preprocess_small_MS_SIMs.py's statistical steps (normalization.py), on every tile's gray plane on
+the GPU in the script's order: banding removal, normalisation, illumination correction, --enhance-contrast. The
+statistics are the tile's own. The percentiles are checked before a model is loaded.
 """
 import argparse
 import json
@@ -108,10 +112,19 @@ def build_parser():
                         "morphology)")
     b.add_argument("--rolling-ball-radius", type=int, default=100, help="radius of the rolling ball's disc (0..256)")
     b.add_argument("--tophat-kernel", type=int, default=301, help="size of the top-hat's ellipse (even: the next odd; 1..513)")
-    b.add_argument("--banding-method", type=str, default="none", choices=["none", "morphological"],
-                   help="banding removal before the illumination method")
+    b.add_argument("--banding-method", type=str, default="none", choices=["none", "morphological", "column"],
+                   help="banding removal before the illumination method (column: every column to the image's mean and "
+                        "deviation)")
     b.add_argument("--morph-width", type=int, default=1, help="width of the banding opening's rectangle (1..513)")
     b.add_argument("--morph-height", type=int, default=512, help="height of the banding opening's rectangle (1..513)")
+    b.add_argument("--column-preserve-global", action="store_true", default=True,
+                   help="--banding-method column: keep the image's mean and deviation (the default, as in "
+                        "preprocess_small_MS_SIMs.py)")
+    n = p.add_argument_group("normalisation of the gray plane (on the device)")
+    n.add_argument("--normalization-method", type=str, default="none", choices=["none", "percentile", "zscore"],
+                   help="after banding removal, before the illumination method (preprocess_small_MS_SIMs.py's methods)")
+    n.add_argument("--percentile-low", type=float, default=1.0, help="lower percentile of --normalization-method percentile")
+    n.add_argument("--percentile-high", type=float, default=99.0, help="upper percentile")
     c = p.add_argument_group("connected components (on the device)")
     c.add_argument("--morph-close-k", type=int, default=0, choices=range(0, 64), metavar="K",
                    help="close the binarised mask with a K x K ellipse before anything else is done with it "
@@ -132,7 +145,7 @@ def build_parser():
 def build_illumination(args):
     """The IlluminationCorrection the flags ask for, or None; ValueError on a size the kernel does not take. Needs no
     device."""
-    if args.illumination_method == "none" and args.banding_method == "none":
+    if args.illumination_method == "none" and args.banding_method in ("none", "column"):   # column: build_normalization
         return None
     import _adipose_pkg  # noqa: F401
     from adipose_amd.illumination import IlluminationCorrection
@@ -142,10 +155,23 @@ def build_illumination(args):
         radius=args.rolling_ball_radius, kernel_size=args.tophat_kernel)
 
 
+def build_normalization(args):
+    """The GrayNormalization the flags ask for, or None; ValueError on percentiles out of order. Needs no device."""
+    if args.banding_method != "column" and args.normalization_method == "none":
+        return None
+    import _adipose_pkg  # noqa: F401
+    from adipose_amd.normalization import GrayNormalization
+    return GrayNormalization(
+        column_banding=args.banding_method == "column", preserve_global=args.column_preserve_global,
+        method=None if args.normalization_method == "none" else args.normalization_method,
+        p_low=args.percentile_low, p_high=args.percentile_high)
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
     try:
         illumination = build_illumination(args)
+        normalization = build_normalization(args)
     except ValueError as e:
         print(f"❌ {e}")
         return 1
@@ -204,8 +230,10 @@ def main(argv=None):
               f"{contrast.tile_size} x {contrast.tile_size} tiles")
     if illumination is not None:
         print(f"✓ Background correction: {illumination}")
+    if normalization is not None:
+        print(f"✓ Gray normalisation: {normalization}")
     model = AdiposeUNet(tile_size=args.tile, dtype=args.dtype, max_batch=args.batch, stain_normalizer=normalizer,
-                        contrast=contrast, illumination=illumination)
+                        contrast=contrast, illumination=illumination, normalization=normalization)
     model.build_model()
     model.load_weights(weights_file)
     mean, std = load_normalization_stats(checkpoint_dir)

@@ -52,7 +52,8 @@ extern "C" {
                               v21: adp_timing_filter; added under v21 (new exports only, nothing changed):
                               adp_morph_pack / adp_morph_bits / adp_morph_unpack;
                               adp_clahe_hist / adp_clahe_lut / adp_clahe_apply, adp_gray_stats, adp_u8_stretch;
-                              adp_gray_morph / adp_gray_bgsum / adp_illum_finish */
+                              adp_gray_morph / adp_gray_bgsum / adp_illum_finish;
+                              adp_gray_colstats / adp_gray_colparams / adp_gray_colnorm / adp_gray_normalize */
 
 typedef void* adp_stream_t; /* hipStream_t */
 
@@ -588,6 +589,46 @@ int adp_gray_bgsum(int N, int H, int W, const uint8_t* src, long long* sums, adp
  * dst uint8 or float32 (dst_f32 != 0) holding the same integers. Also fails on an unknown mode or N > 65535 */
 int adp_illum_finish(int N, int H, int W, const void* v, int v_f32, const uint8_t* b, const long long* sums, int mode,
                      void* dst, int dst_f32, adp_stream_t s);
+
+/* ---- the statistical steps of the gray-image preparation (pre-post-processing_tools/preprocess_small_MS_SIMs.py:249-286
+ *      remove_banding_column_normalize, 92-114 normalize_zscore, 117-138 normalize_percentile; definitions in
+ *      normalization.py). A plane is (N, H, W) uint8, or float32 (the _f32 flag != 0) rounded to nearest and clamped to
+ *      0 .. 255 on load; every image on its own. Exact integer sums, histograms and minima / maxima, then float64
+ *      operations rounded one by one in the definition's order, so exact and independent of N, the grid and the run.
+ *      All stream-ordered, none synchronises. N = 0 returns 0 without a launch. Every call fails (message, nothing
+ *      launched, outputs untouched) on a NULL pointer, N < 0 or N > 65535, H or W < 1, H * W >= 2^31, or an output that
+ *      overlaps an input ------------------------------------------------------------------------------------------- */
+/* rows x columns of the plane that one block of adp_gray_colstats reduces (tests place their shapes around them) */
+#define ADP_GNORM_BAND_ROWS 64
+#define ADP_GNORM_BAND_COLS 256
+/* a plane of more than ADP_GNORM_TALL_BLOCKS such blocks (N * bands) that takes the 16-byte path (uint8, W % 16 == 0,
+ * aligned) is reduced by blocks of ADP_GNORM_TALL_FACTOR bands of rows: fewer atomics per column. The result is the same
+ * integers either way */
+#define ADP_GNORM_TALL_BLOCKS 1024
+#define ADP_GNORM_TALL_FACTOR 4
+#define ADP_GNORM_ZSCORE 0
+#define ADP_GNORM_PERCENTILE 1
+/* colsums (N, W, 2) int64 {S1 = sum v, S2 = sum v^2} and colminmax (N, W, 2) uint32 {min, max} of every column, in one
+ * pass over the plane (integer atomics: exact in any order). The call initialises both */
+int adp_gray_colstats(int N, int H, int W, const void* src, int src_f32, long long* colsums, uint32_t* colminmax,
+                      adp_stream_t s);
+/* from adp_gray_colstats' outputs: col (N, W, 2) float64 {cm, d}: cm = S1 / H, d = sqrt(max(S2 / H - cm * cm, 0)) + 1e-10;
+ * glob (N, 4) float64 {gm, gs, lo, hi}: mean and population deviation of the image from the exact totals, and the
+ * minimum of (min_x - cm_x) / d_x and maximum of (max_x - cm_x) / d_x over the columns */
+int adp_gray_colparams(int N, int H, int W, const long long* colsums, const uint32_t* colminmax, double* col, double* glob,
+                       adp_stream_t s);
+/* dst (N, H, W) uint8 or float32 (dst_f32 != 0) = trunc(clip(t', 0, 255)), t = (v - cm_x) / d_x and
+ * t' = t * gs + gm (preserve_global != 0) or ((t - lo) / ((hi - lo) + 1e-10)) * 255 */
+int adp_gray_colnorm(int N, int H, int W, const void* src, int src_f32, const double* col, const double* glob,
+                     int preserve_global, void* dst, int dst_f32, adp_stream_t s);
+/* dst (N, n_px) uint8 or float32 = table[src] per image; the table is built on the device from hist (N, 256), the
+ * image's histogram as adp_clahe_hist writes it on a 1 x 1 grid:
+ *   ADP_GNORM_ZSCORE      table[i] = trunc(clip((((i - mean) / (std + 1e-10)) + 3) / 6 * 255, 0, 255))
+ *   ADP_GNORM_PERCENTILE  table[i] = trunc(clip((i - lo) / max(hi - lo, 1e-3), 0, 1) * 255), lo / hi the p_low / p_high
+ *                         percentiles (numpy's "linear" method, as adp_u8_stretch finds them)
+ * Also fails on an unknown method, or percentiles that break 0 <= p_low <= p_high <= 100. n_px in 1 .. 2^31 - 1 */
+int adp_gray_normalize(int N, size_t n_px, const void* src, int src_f32, const uint32_t* hist, int method, double p_low,
+                       double p_high, void* dst, int dst_f32, adp_stream_t s);
 
 /* ---- optimizer (Keras Adam / AdamW, :800-806) --------------------------------------------- */
 int adp_adam(size_t n, float* param, const float* grad, float* m, float* v, float lr, float beta1,
