@@ -2,7 +2,7 @@
 
 The reference prepares a gray image in preprocess_ecm_image (pre-post-processing_tools/preprocess_small_MS_SIMs.py:
 462-537): banding removal, normalisation, illumination correction, CLAHE, sharpening. illumination.py has the
-morphological banding removal and the illumination step, contrast.py has CLAHE; this module has
+morphological banding removal and the illumination step, contrast.py has CLAHE, sharpen.py the sharpening; this module has
 
   remove_banding_column_normalize   :249-286   every column to zero mean and unit deviation, then back to the image's
                                                mean and deviation, or to 0 .. 255          (--banding-method column)

@@ -45,6 +45,12 @@ on every chunk of gray planes on the device: normalization.remove_banding, illum
 normalization.normalize, illumination.correct, contrast. The sliding window does the same once on the whole gray image
 and predicts its windows without per-tile steps; per tile the statistics are the tile's. 1-channel networks only.
 Opt-in: with normalization=None every path runs as before.
+
+Sharpening at inference (sharpen.py; preprocess_ecm_image's last step, --sharpen): a predictor with `sharpen` set (a
+sharpen.UnsharpMask) passes every chunk of gray planes through the unsharp mask on the device after `contrast`, as the
+last step before the input is prepared. The sliding window sharpens a gray image once as a whole and predicts its
+windows without per-tile sharpening; per tile the border is the tile's. 1-channel networks only. Opt-in: with
+sharpen=None every path runs as before.
 """
 from __future__ import annotations
 
@@ -92,7 +98,7 @@ class HipUnetPredictor:
     """GPU predictor: predict_single(image, mean, std) -> (S,S) float32 probabilities (main_out)."""
 
     def __init__(self, net, max_batch=8, stain_normalizer=None, tile_filter=None, skip_classes=("empty",), contrast=None,
-                 illumination=None, normalization=None):
+                 illumination=None, normalization=None, sharpen=None):
         self.net = net
         self.device = net.device
         self.max_batch = max_batch
@@ -102,6 +108,7 @@ class HipUnetPredictor:
         self.contrast = contrast                   # contrast.Clahe: every tile's gray plane is enhanced on the device
         self.illumination = illumination           # illumination.IlluminationCorrection: applied before `contrast`
         self.normalization = normalization         # normalization.GrayNormalization: around the banding step (below)
+        self.sharpen = sharpen                     # sharpen.UnsharpMask: applied after `contrast`, the last step
         self.last_tile_classes = None              # classes of the last predict_views call's tiles, in input order
         self._packed_step = None
 
@@ -124,7 +131,7 @@ class HipUnetPredictor:
         every tile's gray plane goes through CLAHE before the input is prepared; with `illumination` set (and
         enhance=True) through the background correction before that; with `normalization` set (and enhance=True) the
         order is normalization.remove_banding, illumination.remove_banding, normalization.normalize,
-        illumination.correct, contrast."""
+        illumination.correct, contrast; with `sharpen` set (and enhance=True) the unsharp mask comes after all of them."""
         contrast = self.contrast if enhance else None
         if contrast is not None and getattr(self.net, "in_ch", 1) != 1:
             raise ValueError("contrast enhancement works on the gray plane of a 1-channel network")
@@ -134,6 +141,9 @@ class HipUnetPredictor:
         normalization = self.normalization if enhance else None
         if normalization is not None and getattr(self.net, "in_ch", 1) != 1:
             raise ValueError("gray normalisation works on the gray plane of a 1-channel network")
+        sharpen = self.sharpen if enhance else None
+        if sharpen is not None and getattr(self.net, "in_ch", 1) != 1:
+            raise ValueError("sharpening works on the gray plane of a 1-channel network")
         n_img = len(images)
         nv = len(views)
         plain = self.stain_normalizer is None and self.tile_filter is None
@@ -171,6 +181,8 @@ class HipUnetPredictor:
                 chunk = illumination(torch.stack([_to_dev(img, self.device) for img in chunk]))
             if contrast is not None:   # one batched CLAHE of the chunk's gray planes (f32 in, f32 out, the same integers)
                 chunk = contrast(torch.stack([_to_dev(img, self.device) for img in chunk]))
+            if sharpen is not None:   # one batched unsharp mask of the chunk's gray planes, the last step (f32 in, f32 out)
+                chunk = sharpen(torch.stack([_to_dev(img, self.device) for img in chunk]))
             for t, img in enumerate(chunk):
                 src = _to_dev(img, self.device)[None]
                 for k, v in enumerate(views):
@@ -205,8 +217,10 @@ class AdiposeUNet:
     predict_single / predict). ``dtype='f32'`` reproduces the reference's fp32 numerics."""
 
     def __init__(self, tile_size=1024, dtype="f32", device="cuda", max_batch=8, stain_normalizer=None,
-                 tile_filter=None, skip_classes=("empty",), contrast=None, illumination=None, normalization=None):
+                 tile_filter=None, skip_classes=("empty",), contrast=None, illumination=None, normalization=None,
+                 sharpen=None):
         self.net = None
+        self.sharpen = sharpen
         self.contrast = contrast
         self.illumination = illumination
         self.normalization = normalization
@@ -228,7 +242,8 @@ class AdiposeUNet:
         self.net = AdiposeV3Net(1, self.tile_size, dtype=self.dtype, device=self.device, init_nb=init_nb, cpad=cpad,
                                 dropout_rate=dropout_rate, deep_supervision=use_deep_supervision)
         self._pred = HipUnetPredictor(self.net, self.max_batch, self.stain_normalizer, self.tile_filter,
-                                      self.skip_classes, self.contrast, self.illumination, self.normalization)
+                                      self.skip_classes, self.contrast, self.illumination, self.normalization,
+                                      self.sharpen)
         return self.net
 
     def load_weights(self, weights_path: str):
@@ -242,6 +257,7 @@ class AdiposeUNet:
         p.contrast = self.contrast
         p.illumination = self.illumination
         p.normalization = self.normalization
+        p.sharpen = self.sharpen
         return p
 
     @property
@@ -514,6 +530,11 @@ class SlidingWindowInference:
             # a gray image is enhanced once as a whole (preprocess_small_MS_SIMs.py enhances before it tiles); its
             # windows are then predicted without per-tile enhancement. RGB windows are enhanced inside predict_views
             img = contrast(img)
+            kw["enhance"] = False
+        sharpen = getattr(model, "sharpen", None)
+        if sharpen is not None and img.dim() == 2:
+            # a gray image is sharpened once as a whole, after its contrast is enhanced (preprocess_ecm_image's last step)
+            img = sharpen(img)
             kw["enhance"] = False
         h, w = img.shape[:2]
         T = self.tile_size

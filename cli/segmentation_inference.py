@@ -28,6 +28,9 @@ its background mean is the tile's own. Sizes are checked against the kernel's li
 --percentile-high 99): preprocess_small_MS_SIMs.py's statistical steps (normalization.py), on every tile's gray plane on
 the GPU in the script's order: banding removal, normalisation, illumination correction, --enhance-contrast. The
 statistics are the tile's own. The percentiles are checked before a model is loaded.
+--sharpen (--sharpen-sigma 1.0, --sharpen-amount 0.5): preprocess_small_MS_SIMs.py's last step, an unsharp mask
+(sharpen.py), on every tile's gray plane on the GPU after --enhance-contrast; the border is the tile's own. The sigma is
+checked against the kernel's blur radius limit before a model is loaded.
 """
 import argparse
 import json
@@ -125,6 +128,12 @@ def build_parser():
                    help="after banding removal, before the illumination method (preprocess_small_MS_SIMs.py's methods)")
     n.add_argument("--percentile-low", type=float, default=1.0, help="lower percentile of --normalization-method percentile")
     n.add_argument("--percentile-high", type=float, default=99.0, help="upper percentile")
+    s = p.add_argument_group("sharpening (on the device)")
+    s.add_argument("--sharpen", action="store_true", default=False,
+                   help="unsharp mask on every tile's gray plane, the last step before the network "
+                        "(preprocess_small_MS_SIMs.py --sharpen)")
+    s.add_argument("--sharpen-sigma", type=float, default=1.0, help="sigma of the unsharp mask's Gaussian (up to about 16)")
+    s.add_argument("--sharpen-amount", type=float, default=0.5, help="strength of the unsharp mask")
     c = p.add_argument_group("connected components (on the device)")
     c.add_argument("--morph-close-k", type=int, default=0, choices=range(0, 64), metavar="K",
                    help="close the binarised mask with a K x K ellipse before anything else is done with it "
@@ -167,11 +176,22 @@ def build_normalization(args):
         p_low=args.percentile_low, p_high=args.percentile_high)
 
 
+def build_sharpen(args):
+    """The UnsharpMask the flags ask for, or None; ValueError on a sigma whose blur radius the kernel does not take, or
+    a non-finite amount. Needs no device."""
+    if not args.sharpen:
+        return None
+    import _adipose_pkg  # noqa: F401
+    from adipose_amd.sharpen import UnsharpMask
+    return UnsharpMask(args.sharpen_sigma, args.sharpen_amount)
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
     try:
         illumination = build_illumination(args)
         normalization = build_normalization(args)
+        sharpen = build_sharpen(args)
     except ValueError as e:
         print(f"❌ {e}")
         return 1
@@ -232,8 +252,10 @@ def main(argv=None):
         print(f"✓ Background correction: {illumination}")
     if normalization is not None:
         print(f"✓ Gray normalisation: {normalization}")
+    if sharpen is not None:
+        print(f"✓ Sharpening: {sharpen} (blur radius {sharpen.radius})")
     model = AdiposeUNet(tile_size=args.tile, dtype=args.dtype, max_batch=args.batch, stain_normalizer=normalizer,
-                        contrast=contrast, illumination=illumination, normalization=normalization)
+                        contrast=contrast, illumination=illumination, normalization=normalization, sharpen=sharpen)
     model.build_model()
     model.load_weights(weights_file)
     mean, std = load_normalization_stats(checkpoint_dir)

@@ -53,7 +53,8 @@ extern "C" {
                               adp_morph_pack / adp_morph_bits / adp_morph_unpack;
                               adp_clahe_hist / adp_clahe_lut / adp_clahe_apply, adp_gray_stats, adp_u8_stretch;
                               adp_gray_morph / adp_gray_bgsum / adp_illum_finish;
-                              adp_gray_colstats / adp_gray_colparams / adp_gray_colnorm / adp_gray_normalize */
+                              adp_gray_colstats / adp_gray_colparams / adp_gray_colnorm / adp_gray_normalize;
+                              adp_gray_blur / adp_gray_sharpen */
 
 typedef void* adp_stream_t; /* hipStream_t */
 
@@ -629,6 +630,30 @@ int adp_gray_colnorm(int N, int H, int W, const void* src, int src_f32, const do
  * Also fails on an unknown method, or percentiles that break 0 <= p_low <= p_high <= 100. n_px in 1 .. 2^31 - 1 */
 int adp_gray_normalize(int N, size_t n_px, const void* src, int src_f32, const uint32_t* hist, int method, double p_low,
                        double p_high, void* dst, int dst_f32, adp_stream_t s);
+
+/* ---- unsharp mask, the last step of the gray-image preparation (preprocess_small_MS_SIMs.py:434-455 sharpen_image;
+ *      definition in sharpen.py). A plane is (N, H, W) uint8, or float32 (the _f32 flag != 0) rounded to nearest and
+ *      clamped to 0 .. 255 on load; every image on its own. taps is a HOST pointer to the r + 1 integer taps q0 .. qr of
+ *      the Gaussian (sharpen.taps), which the call checks (q0 + 2 sum qi = 2^24) and hands to the kernels by value. The
+ *      blur is the exact integer S(y, x) = sum_j q|j| sum_i q|i| v(fold(y + j), fold(x + i)) <= 255 * 2^48 with
+ *      BORDER_REFLECT_101 folded as often as needed (images smaller than r are legal), so exact and independent of the
+ *      grid and the run. r <= ADP_SHARP_FUSED_RMAX is one launch and rowbuf may be NULL; a larger r is two launches
+ *      through rowbuf, a uint32 (N, H, W) plane of row sums the caller supplies. Stream-ordered, no synchronisation.
+ *      N = 0 returns 0 without a launch. Every call fails (message, nothing launched, outputs untouched) on N < 0 or
+ *      N > 65535, H or W < 1, H * W >= 2^31, r outside 0 .. ADP_SHARP_RMAX, taps that do not sum to 2^24, a non-finite
+ *      amount, a NULL pointer (rowbuf when it is needed), or an output or rowbuf that overlaps src or each other --- */
+#define ADP_SHARP_RMAX 64
+#define ADP_SHARP_FUSED_RMAX 16
+/* rows x columns of the output tile one block makes (tests place their shapes around them) */
+#define ADP_SHARP_TILE_ROWS 32
+#define ADP_SHARP_TILE_COLS 64
+/* S_out (N, H, W) int64 = S */
+int adp_gray_blur(int N, int H, int W, const void* src, int src_f32, const uint32_t* taps, int r, uint32_t* rowbuf,
+                  long long* S_out, adp_stream_t s);
+/* dst (N, H, W) uint8 or float32 (dst_f32 != 0) = trunc(clip(t, 0, 255)), t = f64(v) + amount * (f64(v * 2^48 - S) * 2^-48)
+ * in float64, each operation rounded on its own */
+int adp_gray_sharpen(int N, int H, int W, const void* src, int src_f32, const uint32_t* taps, int r, double amount,
+                     uint32_t* rowbuf, void* dst, int dst_f32, adp_stream_t s);
 
 /* ---- optimizer (Keras Adam / AdamW, :800-806) --------------------------------------------- */
 int adp_adam(size_t n, float* param, const float* grad, float* m, float* v, float lr, float beta1,
