@@ -14,30 +14,31 @@ inline int nblk(size_t n, int cap = 8192) {
   return (int)(b < (size_t)cap ? (b ? b : 1) : cap);
 }
 
-// View v of the input image A (S x S): V[a][b] = A[g_v(a,b)], matching the reference transforms
+// View v of the input image A (H x W): V[a][b] = A[g_v(a,b)], matching the reference transforms
 // 0 ident, 1 rot90 (np.rot90 k=1, CCW), 2 rot180, 3 rot270, 4 flipH (axis 1), 5 flipV (axis 0),
-// 6 flipH(rot90), 7 flipV(rot90).
-ADP_DEV void view_src(int v, int a, int b, int S, int& i, int& j) {
+// 6 flipH(rot90), 7 flipV(rot90). Row indices mirror in H and column indices in W; the views that
+// transpose (1, 3, 6, 7) and view 2 are only launched on squares, where the two are the same number.
+ADP_DEV void view_src(int v, int a, int b, int H, int W, int& i, int& j) {
   switch (v) {
-    case 1: i = b; j = S - 1 - a; break;
-    case 2: i = S - 1 - a; j = S - 1 - b; break;
-    case 3: i = S - 1 - b; j = a; break;
-    case 4: i = a; j = S - 1 - b; break;
-    case 5: i = S - 1 - a; j = b; break;
-    case 6: i = S - 1 - b; j = S - 1 - a; break;
+    case 1: i = b; j = W - 1 - a; break;
+    case 2: i = H - 1 - a; j = W - 1 - b; break;
+    case 3: i = H - 1 - b; j = a; break;
+    case 4: i = a; j = W - 1 - b; break;
+    case 5: i = H - 1 - a; j = b; break;
+    case 6: i = H - 1 - b; j = W - 1 - a; break;
     case 7: i = b; j = a; break;
     default: i = a; j = b; break;
   }
 }
 // inverse: original pixel (i,j) is predicted at view pixel (a,b)
-ADP_DEV void view_dst(int v, int i, int j, int S, int& a, int& b) {
+ADP_DEV void view_dst(int v, int i, int j, int H, int W, int& a, int& b) {
   switch (v) {
-    case 1: a = S - 1 - j; b = i; break;
-    case 2: a = S - 1 - i; b = S - 1 - j; break;
-    case 3: a = j; b = S - 1 - i; break;
-    case 4: a = i; b = S - 1 - j; break;
-    case 5: a = S - 1 - i; b = j; break;
-    case 6: a = S - 1 - j; b = S - 1 - i; break;
+    case 1: a = W - 1 - j; b = i; break;
+    case 2: a = H - 1 - i; b = W - 1 - j; break;
+    case 3: a = j; b = H - 1 - i; break;
+    case 4: a = i; b = W - 1 - j; break;
+    case 5: a = H - 1 - i; b = j; break;
+    case 6: a = W - 1 - j; b = H - 1 - i; break;
     case 7: a = j; b = i; break;
     default: a = i; b = j; break;
   }
@@ -54,7 +55,7 @@ __global__ void prep_kernel(int N, int H, int W, int Cin, const float* src, long
     size_t t = p / W;
     int a = (int)(t % H), n = (int)(t / H);
     int i, j;
-    view_src(view, a, b, H, i, j);
+    view_src(view, a, b, H, W, i, j);
     const float* s = src + (size_t)n * img_stride + ((size_t)i * row_stride + j) * Cin;
     T* d = dst + p * Cs;
     for (int c = 0; c < Cs; ++c) d[c] = from_f<T>(c < Cin ? __fdiv_rn(__fsub_rn(s[c], mean), den) : 0.f);
@@ -70,7 +71,7 @@ __global__ void tta_merge_kernel(int H, int W, int nv, ViewList views, const flo
     float s = 0.f;
     for (int k = 0; k < nv; ++k) {
       int a, b;
-      view_dst(views.v[k], i, j, H, a, b);
+      view_dst(views.v[k], i, j, H, W, a, b);
       s += probs[(size_t)k * total + (size_t)a * W + b];
     }
     out[p] = s / (float)nv;

@@ -10,7 +10,7 @@
 //                  the trapezoid area of the ROC curve over distinct thresholds);
 //        AP      = sum_g (pos_g / P) * precision at threshold t_g, precision = positives / pixels >= t_g
 //                  (the step-wise sum of average_precision_score over distinct thresholds);
-//      terms are f64, reduced per block and added with f64 atomics;
+//      terms are f64, reduced per block to one partial pair each, the partials summed by one block in a fixed order;
 //   3. NaN when only one class is present (the reference's early return).
 #include <hipcub/hipcub.hpp>
 
@@ -65,26 +65,47 @@ __global__ void auc_group_kernel(size_t n, const uint32_t* __restrict__ key, con
     r1[threadIdx.x >> 6] = ap;
   }
   __syncthreads();
-  if (threadIdx.x == 0) {
+  if (threadIdx.x == 0) {   // one partial pair per block, no atomics: the order of the final sum is fixed
     double a = 0.0, b = 0.0;
     for (int w = 0; w < TPB / 64; ++w) { a += r0[w]; b += r1[w]; }
-    atomicAdd(acc, a);
-    atomicAdd(acc + 1, b);
+    acc[2 * blockIdx.x] = a;
+    acc[2 * blockIdx.x + 1] = b;
   }
 }
 
-__global__ void auc_final_kernel(size_t n, const uint32_t* __restrict__ cpos, const double* __restrict__ acc,
-                                 double* __restrict__ out) {
+// one block: the `nparts` partial pairs summed in an order that depends on nparts alone, so the same input gives
+// the same bits on every run and stream (the ROC terms are exact in any order; the AP terms are not)
+__global__ void auc_final_kernel(size_t n, int nparts, const uint32_t* __restrict__ cpos,
+                                 const double* __restrict__ acc, double* __restrict__ out) {
+  double roc = 0.0, ap = 0.0;
+  for (int b = threadIdx.x; b < nparts; b += TPB) {
+    roc += acc[2 * b];
+    ap += acc[2 * b + 1];
+  }
+  __shared__ double r0[TPB / 64], r1[TPB / 64];
+  for (int o = 32; o > 0; o >>= 1) {
+    roc += __shfl_xor(roc, o, 64);
+    ap += __shfl_xor(ap, o, 64);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    r0[threadIdx.x >> 6] = roc;
+    r1[threadIdx.x >> 6] = ap;
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  roc = ap = 0.0;
+  for (int w = 0; w < TPB / 64; ++w) { roc += r0[w]; ap += r1[w]; }
   const double P = (double)cpos[n - 1], N = (double)n - P;
   const bool ok = P > 0.0 && N > 0.0;
-  out[0] = ok ? acc[0] / (P * N) : __builtin_nan("");
-  out[1] = ok ? acc[1] / P : __builtin_nan("");
+  out[0] = ok ? roc / (P * N) : __builtin_nan("");
+  out[1] = ok ? ap / P : __builtin_nan("");
 }
 
 }  // namespace
 
 extern "C" int adp_auc_metrics(size_t n, const float* pred, const float* truth, double* out, adp_stream_t st) {
-  ADP_REQUIRE(pred && truth && out && n > 0 && n < (size_t)UINT32_MAX, "adp_auc_metrics: 0 < n < 2^32 pixels");
+  ADP_REQUIRE(pred && truth && out && n > 0 && n <= (size_t)INT_MAX,
+              "adp_auc_metrics: 0 < n <= INT_MAX pixels (hipCUB takes an int count)");
   hipStream_t s = (hipStream_t)st;
   size_t sort_b = 0, sum_b = 0, max_b = 0;
   uint32_t* nul = nullptr;
@@ -94,7 +115,9 @@ extern "C" int adp_auc_metrics(size_t n, const float* pred, const float* truth, 
               "adp_auc_metrics: temporary-storage query failed");
   const size_t tmp_b = (std::max(sort_b, std::max(sum_b, max_b)) + 255) / 256 * 256;
   const size_t arr = (n * 4 + 255) / 256 * 256;
-  char* w = static_cast<char*>(adp::scratch(adp::Slot::AucSort, 6 * arr + tmp_b + 256, s));
+  constexpr int MAX_GRID = 4096;
+  constexpr size_t acc_b = (size_t)MAX_GRID * 2 * sizeof(double);   // one (roc, ap) partial pair per block
+  char* w = static_cast<char*>(adp::scratch(adp::Slot::AucSort, 6 * arr + acc_b + tmp_b, s));
   if (!w) return -2;
   uint32_t* key_in = reinterpret_cast<uint32_t*>(w);
   uint32_t* key_out = reinterpret_cast<uint32_t*>(w + arr);
@@ -103,8 +126,8 @@ extern "C" int adp_auc_metrics(size_t n, const float* pred, const float* truth, 
   uint32_t* cpos = reinterpret_cast<uint32_t*>(w + 4 * arr);
   uint32_t* start = reinterpret_cast<uint32_t*>(w + 5 * arr);
   double* acc = reinterpret_cast<double*>(w + 6 * arr);
-  void* tmp = w + 6 * arr + 256;
-  const int grid = (int)std::min<size_t>((n + TPB - 1) / TPB, 4096);
+  void* tmp = w + 6 * arr + acc_b;
+  const int grid = (int)std::min<size_t>((n + TPB - 1) / TPB, MAX_GRID);
   hipLaunchKernelGGL(auc_prep_kernel, dim3(grid), dim3(TPB), 0, s, n, pred, truth, key_in, lab_in);
   ADP_REQUIRE(hipcub::DeviceRadixSort::SortPairs(tmp, sort_b, key_in, key_out, lab_in, lab_out, (int)n, 0, 32, s) ==
                   hipSuccess, "adp_auc_metrics: radix sort failed");
@@ -113,9 +136,8 @@ extern "C" int adp_auc_metrics(size_t n, const float* pred, const float* truth, 
   hipLaunchKernelGGL(auc_start_kernel, dim3(grid), dim3(TPB), 0, s, n, key_out, lab_in);   // sort inputs are free
   ADP_REQUIRE(hipcub::DeviceScan::InclusiveScan(tmp, max_b, lab_in, start, hipcub::Max(), (int)n, s) == hipSuccess,
               "adp_auc_metrics: max-scan failed");
-  ADP_REQUIRE(hipMemsetAsync(acc, 0, 2 * sizeof(double), s) == hipSuccess, "adp_auc_metrics: memset failed");
   hipLaunchKernelGGL(auc_group_kernel, dim3(grid), dim3(TPB), 0, s, n, key_out, cpos, start, acc);
-  hipLaunchKernelGGL(auc_final_kernel, dim3(1), dim3(1), 0, s, n, cpos, acc, out);
+  hipLaunchKernelGGL(auc_final_kernel, dim3(1), dim3(TPB), 0, s, n, grid, cpos, acc, out);
   return adp::check_launch("adp_auc_metrics");
 }
 
