@@ -54,7 +54,8 @@ extern "C" {
                               adp_clahe_hist / adp_clahe_lut / adp_clahe_apply, adp_gray_stats, adp_u8_stretch;
                               adp_gray_morph / adp_gray_bgsum / adp_illum_finish;
                               adp_gray_colstats / adp_gray_colparams / adp_gray_colnorm / adp_gray_normalize;
-                              adp_gray_blur / adp_gray_sharpen */
+                              adp_gray_blur / adp_gray_sharpen;
+                              adp_fat_counts */
 
 typedef void* adp_stream_t; /* hipStream_t */
 
@@ -654,6 +655,22 @@ int adp_gray_blur(int N, int H, int W, const void* src, int src_f32, const uint3
  * in float64, each operation rounded on its own */
 int adp_gray_sharpen(int N, int H, int W, const void* src, int src_f32, const uint32_t* taps, int r, double amount,
                      uint32_t* rowbuf, void* dst, int dst_f32, adp_stream_t s);
+
+/* ---- per-tile fat counts of the tile-level "Has Fat / No Fat" evaluation (tile_classification_evaluation.py:211-226
+ *      calculate_fat_percentage of the prediction, and of the ground truth after its normalisation :478-489; definition
+ *      in tile_classification.py). Integers only: the result does not depend on the grid or the run. Stream-ordered, no
+ *      synchronisation. N = 0 returns 0 without a launch. The call fails (message, nothing launched, out untouched) on
+ *      N < 0 or N > 65535, n_px < 1 (or above 2^36), both inputs NULL, out NULL, or a cut outside 0 .. 256 --- */
+/* rows x 1 pixels that one block counts (tests place their shapes around it) */
+#define ADP_FAT_BLOCK_PX 32768
+/* out (N, 4) uint64, zeroed by the call, per image i of n_px pixels:
+ *   out[4i+0] = #(pred[i] > pred_thr)      IEEE '>' in float32: NaN on either side counts nothing
+ *   out[4i+1] = max gt[i]                  (0 for gt == NULL)
+ *   out[4i+2] = #(gt[i] >= cut_raw)        cut_* in 0 .. 256 (256: nothing counts)
+ *   out[4i+3] = #(gt[i] >= cut_scaled)
+ * pred (N, n_px) float32 or NULL, gt (N, n_px) uint8 or NULL, not both NULL; columns of a NULL input stay 0. */
+int adp_fat_counts(int N, size_t n_px, const float* pred, float pred_thr, const uint8_t* gt, int cut_raw,
+                   int cut_scaled, unsigned long long* out, adp_stream_t s);
 
 /* ---- optimizer (Keras Adam / AdamW, :800-806) --------------------------------------------- */
 int adp_adam(size_t n, float* param, const float* grad, float* m, float* v, float lr, float beta1,
