@@ -143,6 +143,7 @@ _SIGS = {
     "adp_gray_blur": [_I, _I, _I, _P, _I, C.POINTER(C.c_uint32), _I, _P, _P, _P],
     "adp_gray_sharpen": [_I, _I, _I, _P, _I, C.POINTER(C.c_uint32), _I, C.c_double, _P, _P, _I, _P],
     "adp_fat_counts": [_I, _S, _P, _F, _P, _I, _I, _P, _P],
+    "adp_poly_raster": [_I, _I, _I, _P, _P, _P, _I, C.c_longlong, _P, _P],
     "adp_create": [_P, _I, _P],
     "adp_destroy": [_P],
     "adp_param_size": [_P, C.c_char_p, _I, C.POINTER(C.c_size_t)],

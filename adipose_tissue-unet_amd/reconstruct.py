@@ -41,7 +41,7 @@ from .predictor import (TTA_VIEWS, AdiposeUNet, BandCanvas, GaussianBlender, Lin
 __all__ = ["parse_tile_filename", "group_tiles_by_slide", "get_source_image_dimensions",
            "infer_full_image_dimensions", "get_full_image_dimensions", "find_missing_tiles",
            "create_expected_grid", "reconstruct_slide", "create_overlay", "create_4panel_comparison",
-           "create_reconstruction_log", "reconstruct_all_slides"]
+           "create_reconstruction_log", "reconstruct_all_slides", "find_annotation_jsons", "annotation_ground_truth"]
 
 
 # ------------------------------------------------------------------------------ tile grid
@@ -306,7 +306,7 @@ def create_reconstruction_log(args, output_dir: Path, slide_results: List[Dict])
                           "use_tta": args.use_tta, "tta_mode": args.tta_mode if args.use_tta else None,
                           "boundary_refine": args.boundary_refine,
                           "refine_kernel": args.refine_kernel if args.boundary_refine else None,
-                          **_component_settings(args)},
+                          **_component_settings(args), **_annotation_settings(args)},
         "slides_processed": len(slide_results),
         "slide_results": slide_results,
         "summary_statistics": {
@@ -338,6 +338,45 @@ def _component_settings(args):
     return out
 
 
+def _annotation_settings(args):
+    """The ground-truth-from-annotations settings of a run, for the log: nothing without --annotations-dir."""
+    if not getattr(args, "annotations_dir", None):
+        return {}
+    return {"annotations_dir": str(args.annotations_dir), "annotation_class": getattr(args, "annotation_class", "fat"),
+            "annotation_subtract_class": getattr(args, "annotation_subtract_class", "bubbles"),
+            "annotation_min_confidence": int(getattr(args, "annotation_min_confidence", 2)),
+            "gt_morph_close_k": int(getattr(args, "gt_morph_close_k", 0) or 0),
+            "gt_min_cc_px": int(getattr(args, "gt_min_cc_px", 0) or 0)}
+
+
+def find_annotation_jsons(annotations_dir, cls: str) -> Dict[str, Path]:
+    """image stem -> the JSON of class `cls` under <annotations_dir>/<cls>/ (the reference's Masks folder), matched with
+    parse_image_stem_from_json; of several for one stem the last in sorted order wins, with a warning (the builder
+    overwrites the mask it wrote before)."""
+    from .annotations import parse_image_stem_from_json
+    found: Dict[str, Path] = {}
+    for jp in sorted((Path(annotations_dir) / cls).glob("*.json")):
+        stem = parse_image_stem_from_json(jp, cls)
+        if stem in found:
+            warnings.warn(f"{stem}: {jp.name} replaces {found[stem].name}")
+        found[stem] = jp
+    return found
+
+
+def annotation_ground_truth(target_json, subtract_json, full_shape, min_confidence=2, morph_close_k=0, min_cc_px=0):
+    """The slide's ground truth from the annotators' JSON at full resolution, f32 0 / 1 of full_shape: the reference's
+    chain create_binary_mask -> minus the subtract class -> morph_close -> remove_small_components (annotations.py).
+    A device tensor where there is a device (nothing leaves it), the numpy path's array otherwise."""
+    from . import annotations as an
+    H, W = int(full_shape[0]), int(full_shape[1])
+    polys, _ = an.load_json_annotations(target_json, min_confidence)
+    sub = an.load_json_annotations(subtract_json, min_confidence)[0] if subtract_json is not None else None
+    if not torch.cuda.is_available():
+        return an.target_mask_np(polys, sub, H, W, morph_close_k, min_cc_px).astype(np.float32)
+    from . import morphology
+    return morphology.unpack(an.target_mask_bits(polys, sub, H, W, morph_close_k, min_cc_px), W, torch.float32)
+
+
 def reconstruct_all_slides(args, model=None, process_group=None):
     """:586-866 — per slide: coverage check, dimensions, reconstruction, TIFF / PNG / metrics outputs.
     ``model`` overrides building AdiposeUNet from args.weights (tests, custom predictors).
@@ -348,7 +387,23 @@ def reconstruct_all_slides(args, model=None, process_group=None):
     8-connected components of fewer than min_cc_px pixels are removed (components.py); the 0 / 1 mask takes the
     prediction's place in prediction_mask.tif, the overlays and the metrics. args.cell_stats: cell_stats.csv with one
     row per slide, from the mask that is written; args.cell_shapes: cell_shapes.csv, likewise (with both, the mask is
-    labelled once)."""
+    labelled once).
+    args.annotations_dir (the reference's Masks folder, <class>/*.json): a slide whose stem has a JSON of
+    args.annotation_class gets its ground truth from the polygons at the slide's full_shape (annotation_ground_truth:
+    raster, minus args.annotation_subtract_class unless "none" or that slide has no such JSON, closed with
+    args.gt_morph_close_k, without components below args.gt_min_cc_px); its mask tiles are neither read nor blended.
+    A slide without one keeps the blended mask tiles. With a process group only rank 0 rasterises. The log and the
+    per-slide metrics JSON then carry ground_truth_source."""
+    ann_dir = getattr(args, "annotations_dir", None)
+    ann_cls = getattr(args, "annotation_class", "fat")
+    ann_sub = getattr(args, "annotation_subtract_class", "bubbles")
+    gt_close_k, gt_min_cc = int(getattr(args, "gt_morph_close_k", 0) or 0), int(getattr(args, "gt_min_cc_px", 0) or 0)
+    if not 0 <= gt_close_k <= 63:
+        raise ValueError("gt_morph_close_k must be in 0..63")
+    if ann_dir and not (Path(ann_dir) / ann_cls).is_dir():   # (a mistyped folder must not fall back to the mask tiles)
+        raise FileNotFoundError(f"Annotation directory not found: {Path(ann_dir) / ann_cls}")
+    ann_json = find_annotation_jsons(ann_dir, ann_cls) if ann_dir else {}
+    sub_json = find_annotation_jsons(ann_dir, ann_sub) if ann_dir and ann_sub and ann_sub != "none" else {}
     min_cc_px, cell_stats = int(getattr(args, "min_cc_px", 0) or 0), bool(getattr(args, "cell_stats", False))
     cell_shapes = bool(getattr(args, "cell_shapes", False))
     morph_close_k = int(getattr(args, "morph_close_k", 0) or 0)
@@ -402,11 +457,20 @@ def reconstruct_all_slides(args, model=None, process_group=None):
             full_shape = (side, side)
         else:
             full_shape = get_full_image_dimensions(slide_id, positions, args.tile_size, args.stride, args.data_root)
+        from_json = slide_id in ann_json
+        if from_json:   # the mask tiles are neither read nor blended
+            tiles_info = [(r, c, img, None) for r, c, img, _ in tiles_info]
         full_rgb, full_pred, full_gt = reconstruct_slide(
             model, tiles_info, full_shape, args.tile_size, args.stride, train_mean, train_std, blender, refiner,
             args.use_tta, args.tta_mode, process_group=process_group, return_device=post)
         if not rank0:
             continue
+        if from_json:
+            full_gt = annotation_ground_truth(ann_json[slide_id], sub_json.get(slide_id), full_shape,
+                                              int(getattr(args, "annotation_min_confidence", 2)), gt_close_k, gt_min_cc)
+            if not post and isinstance(full_gt, torch.Tensor):
+                full_gt = full_gt.cpu().numpy()
+            print(f"  Ground truth: {ann_json[slide_id].name} ({int(full_gt.sum())} px)")
         if post:   # the 64 M-pixel planes are still on the device
             from . import components as cc
             if morph_close_k > 0:   # threshold -> close -> small components -> statistics
@@ -428,7 +492,8 @@ def reconstruct_all_slides(args, model=None, process_group=None):
                 cell_rows.append(cc.cell_stats_row(slide_id, st))
                 print(f"  Cells: {st['num_cells']} (coverage {st['tissue_coverage']:.1%})")
             full_rgb, full_pred = full_rgb.cpu().numpy(), full_pred.cpu().numpy()
-            full_gt = None if full_gt is None else full_gt.cpu().numpy()
+            if isinstance(full_gt, torch.Tensor):
+                full_gt = full_gt.cpu().numpy()
         slide_dir = output_dir / slide_id
         slide_dir.mkdir(parents=True, exist_ok=True)
         _save_tiff(slide_dir / "original_image.tif", (full_rgb * 255).astype(np.uint8))
@@ -465,6 +530,8 @@ def reconstruct_all_slides(args, model=None, process_group=None):
                                   "tiles_rows": info["row_range"][1] - info["row_range"][0] + 1,
                                   "tiles_cols": info["col_range"][1] - info["col_range"][0] + 1},
                    "metrics": metrics if full_gt is not None else None}
+            if ann_dir:   # only then: the JSON of a run without the flag is what it was
+                res["ground_truth_source"] = "annotations" if from_json else "mask_tiles" if full_gt is not None else None
             results.append(res)
             mp = output_dir / "metrics" / f"{slide_id}_metrics.json"
             mp.parent.mkdir(parents=True, exist_ok=True)

@@ -48,6 +48,21 @@ def build_parser():
     c.add_argument("--cell-shapes", action="store_true", default=False,
                    help="write cell_shapes.csv: per slide num_cells, mean / median perimeter, circularity, aspect ratio "
                         "and eccentricity of the cells (--cell-min-area)")
+    g = p.add_argument_group("ground truth from the annotators' polygons (rasterised on the device at full resolution)")
+    g.add_argument("--annotations-dir", type=str, default=None, metavar="DIR",
+                   help="the builder's Masks folder (<class>/*.json): a slide whose stem has a JSON gets its ground truth "
+                        "from the polygons instead of the blended mask tiles")
+    g.add_argument("--annotation-class", type=str, default="fat", help="class folder of the target polygons")
+    g.add_argument("--annotation-subtract-class", type=str, default="bubbles",
+                   help="class whose polygons are subtracted (build_dataset.py --subtract-class; 'none' = off; a slide "
+                        "without such a JSON is not subtracted)")
+    g.add_argument("--annotation-min-confidence", type=int, default=2,
+                   help="records below this confidenceScore are left out (build_dataset.py --test-min-confidence)")
+    g.add_argument("--gt-morph-close-k", type=int, default=0, choices=range(0, 64), metavar="K",
+                   help="close the rasterised ground truth with a K x K ellipse (build_dataset.py --morph-close-k; 0 = off)")
+    g.add_argument("--gt-min-cc-px", type=int, default=0,
+                   help="remove the ground truth's 8-connected components below this many pixels "
+                        "(build_dataset.py --min-cc-px; 0 = off)")
     return p
 
 

@@ -55,7 +55,8 @@ extern "C" {
                               adp_gray_morph / adp_gray_bgsum / adp_illum_finish;
                               adp_gray_colstats / adp_gray_colparams / adp_gray_colnorm / adp_gray_normalize;
                               adp_gray_blur / adp_gray_sharpen;
-                              adp_fat_counts */
+                              adp_fat_counts;
+                              adp_poly_raster */
 
 typedef void* adp_stream_t; /* hipStream_t */
 
@@ -523,6 +524,31 @@ int adp_morph_bits(int N, int H, int W, const unsigned long long* src, unsigned 
 /* the plane as 0 / 1 uint8 and / or 0.0 / 1.0 f32, (N, H, W) each (either may be NULL, not both) */
 int adp_morph_unpack(int N, int H, int W, const unsigned long long* bits, uint8_t* out_u8, float* out_f32,
                      adp_stream_t s);
+
+/* ---- annotation polygons -> ground-truth planes (create_binary_mask, Segmentation/build_dataset.py:903-911: one
+ *      cv2.fillPoly over all polygons of an image), in the plane format above. mask = interior | boundary:
+ *        interior(y, x) = parity over every non-horizontal edge of every polygon of the image of
+ *                         [ylo <= y < yhi and X(y) <= x], X(y) = xlo + (y - ylo)(xhi - xlo) / (yhi - ylo) exactly
+ *                         (even-odd filling: where two polygons overlap the interior cancels)
+ *        boundary       = every edge's 8-connected line from the endpoint (xa, ya) with the smaller x, dx = xb - xa,
+ *                         dy = yb - ya, s = sign(dy): |dy| > dx: (xa + floor((2 dx k + |dy| - 1) / (2 |dy|)), ya + s k),
+ *                         k = 0 .. |dy|; otherwise (xa + k, ya + s floor((2 |dy| k + dx - 1) / (2 dx))), k = 0 .. dx
+ *                         (one point for dx = dy = 0); only pixels inside the raster count
+ *      A restatement of OpenCV's construction: parity with cv2.fillPoly itself is unpinned (OpenCV clips a line to the
+ *      image before it walks it). Integers only (int64): the words do not depend on the grid or the run. Stream-ordered,
+ *      no synchronisation, no scratch. N = 0 returns 0 without a launch --------------------------------------------- */
+/* vertices are accepted in |x|, |y| <= ADP_POLY_COORD_MAX (an edge with a vertex beyond it takes no part) */
+#define ADP_POLY_COORD_MAX 16777216
+/* words of a row that one step of the row scan covers (tests place their widths around it) */
+#define ADP_POLY_SCAN_WORDS 64
+/* bits (N, H, ceil(W / 64)) = the raster of the polygons: xy (V, 2) int32 vertices (x = column, y = row; they may lie
+ * outside the raster), polygon p is the cyclic run xy[poly_off[p] .. poly_off[p + 1]) (edges join consecutive vertices
+ * and the last to the first; an empty run is no polygon), image n has the polygons [img_off[n], img_off[n + 1]).
+ * poly_off (P + 1) and img_off (N + 1) ascend from 0 to V and to P; a vertex or a polygon that they do not bracket
+ * takes no part. All four are DEVICE pointers. Fails (message, nothing launched) on a NULL pointer (with N > 0), N < 0,
+ * H or W < 1, P < 0, V < 0 or V >= 2^31 */
+int adp_poly_raster(int N, int H, int W, const int* xy, const int* poly_off, const int* img_off, int P, long long V,
+                    unsigned long long* bits, adp_stream_t s);
 
 /* ---- contrast-limited adaptive histogram equalisation of 8-bit gray planes (cv2.createCLAHE(clip_limit, (tx, ty))
  *      .apply: pre-post-processing_tools/preprocess_small_MS_SIMs.py:393-431 --enhance-contrast,
