@@ -142,6 +142,8 @@ _SIGS = {
     "adp_gray_normalize": [_I, _S, _P, _I, _P, _I, C.c_double, C.c_double, _P, _I, _P],
     "adp_gray_blur": [_I, _I, _I, _P, _I, C.POINTER(C.c_uint32), _I, _P, _P, _P],
     "adp_gray_sharpen": [_I, _I, _I, _P, _I, C.POINTER(C.c_uint32), _I, C.c_double, _P, _P, _I, _P],
+    "adp_resample_u8": [_I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _I, _P, _P, _P],
+    "adp_resample_nearest_u8": [_I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P],
     "adp_fat_counts": [_I, _S, _P, _F, _P, _I, _I, _P, _P],
     "adp_poly_raster": [_I, _I, _I, _P, _P, _P, _I, C.c_longlong, _P, _P],
     "adp_create": [_P, _I, _P],

@@ -41,6 +41,7 @@ enum class Slot {
   StainPart,     // adp_stain_lab_stats: one row of six f64 sums per block
   TileQcPart,    // adp_tile_qc: one row of three int64 sums per block
   CcScan,        // adp_cc_table / adp_cc_relabel: the ranks of the roots and the scan's temporary
+  ResampleTables,   // adp_resample_u8 / adp_resample_nearest_u8: the axes' bounds and taps, or index tables
   Count
 };
 void* scratch(Slot slot, size_t bytes, hipStream_t s);

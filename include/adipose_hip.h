@@ -56,7 +56,8 @@ extern "C" {
                               adp_gray_colstats / adp_gray_colparams / adp_gray_colnorm / adp_gray_normalize;
                               adp_gray_blur / adp_gray_sharpen;
                               adp_fat_counts;
-                              adp_poly_raster */
+                              adp_poly_raster;
+                              adp_resample_u8 / adp_resample_nearest_u8 */
 
 typedef void* adp_stream_t; /* hipStream_t */
 
@@ -681,6 +682,39 @@ int adp_gray_blur(int N, int H, int W, const void* src, int src_f32, const uint3
  * in float64, each operation rounded on its own */
 int adp_gray_sharpen(int N, int H, int W, const void* src, int src_f32, const uint32_t* taps, int r, double amount,
                      uint32_t* rowbuf, void* dst, int dst_f32, adp_stream_t s);
+
+/* ---- Pillow-exact resampling of 8-bit images (pre-post-processing_tools/ECM_scaling.py:175, :184: an ECM image brought
+ *      to its Pseudocolored counterpart's size with PIL.Image.resize(size, Image.LANCZOS); definition in resample.py).
+ *      src is (N, H, W, C) uint8 and dst (N, Ho, Wo, C) uint8, C in 1 .. 4, channels interleaved; every image and channel
+ *      on its own. The tables are HOST arrays (resample.coefficients / nearest_table make them): the call checks them,
+ *      copies them into the stream's workspace and has read them when it returns. Integers only: the result does not
+ *      depend on the grid, the form or the run. Stream-ordered, no device synchronisation (the first use of a stream
+ *      and a larger table grow its workspace). N = 0 returns 0 without a launch. Every call fails (message, nothing
+ *      launched, outputs untouched) on N < 0 or N > 65535, C outside 1 .. 4, an extent < 1, H * W * C, Ho * Wo * C or
+ *      H * Wo * C >= 2^31, a NULL pointer that is needed, a table that breaks its rules below, or buffers that overlap -- */
+#define ADP_RESAMPLE_KMAX 193 /* taps per output: Lanczos down to 1 / 32, bicubic 1 / 48, bilinear 1 / 96, box 1 / 192 */
+/* rows x columns of the output tile one block of the fused form makes, and the bytes of LDS a block may hold: the fused
+ * form runs when the most input rows a row tile spans, times ADP_RESAMPLE_TILE_COLS * C, fit them (tests place their
+ * shapes around all three) */
+#define ADP_RESAMPLE_TILE_ROWS 32
+#define ADP_RESAMPLE_TILE_COLS 64
+#define ADP_RESAMPLE_LDS_BYTES 32768
+/* The convolution filters. Per axis with n inputs and m outputs: bounds [m][2] int32 {lo, cnt} and taps [m][ks] int32
+ * (row i: the cnt taps of output i, read from input lo on; entries beyond cnt are not read);
+ *   one pass: out = clamp((2^21 + sum_j taps[i][j] * v[lo + j]) >> 22, 0, 255) in int32, the shift arithmetic
+ * The horizontal pass (xb, xk, xks; W -> Wo) runs first and makes a uint8 image, the vertical pass (yb, yk, yks;
+ * H -> Ho) runs on it. An axis whose extent does not change is skipped and its tables are not read (they may be NULL);
+ * with neither changed dst is a copy of src. A table must hold 0 <= lo, 0 <= cnt <= ks <= ADP_RESAMPLE_KMAX,
+ * lo + cnt <= n, lo and lo + cnt never descending with i, and 2^21 + 255 sum_j |taps[i][j]| < 2^31. When both extents
+ * change the call is one fused launch if the tile fits (above) and option resample_fused (adp_set_option: -1 auto,
+ * 0 never, 1 whenever it fits; auto is 1) allows it, otherwise two launches through tmp, a uint8 buffer of
+ * N * H * Wo * C bytes, which then must be non-NULL. dst must not overlap src; tmp, when used, neither */
+int adp_resample_u8(int N, int H, int W, int C, int Ho, int Wo, const uint8_t* src, const int* xb, const int* xk, int xks,
+                    const int* yb, const int* yk, int yks, uint8_t* tmp, uint8_t* dst, adp_stream_t s);
+/* Nearest: dst[n][y][x][c] = src[n][yi[y]][xi[x]][c]; xi (Wo) and yi (Ho) int32 HOST arrays with every index inside
+ * 0 .. W - 1 and 0 .. H - 1 */
+int adp_resample_nearest_u8(int N, int H, int W, int C, int Ho, int Wo, const uint8_t* src, const int* xi, const int* yi,
+                            uint8_t* dst, adp_stream_t s);
 
 /* ---- per-tile fat counts of the tile-level "Has Fat / No Fat" evaluation (tile_classification_evaluation.py:211-226
  *      calculate_fat_percentage of the prediction, and of the ground truth after its normalisation :478-489; definition
